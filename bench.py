@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- mapped Gbp/s of the `-cx lr` seed-chain-align hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: workload + index (untimed), W warm-up steps, K timed steps, the outputs of the last step when --dump-outputs is
+given, one JSON line (`value`, `ms_per_step`, `roofline_path` from the counters of the timed steps).  Everything else below -- the other placement, `rank_share`, `file_out`,
+`resident`, the isolated passes and their per-kernel roofline, `cpu_baseline` and the parity strings, `linear` / `bubble50` / `asm` -- runs with --full only (each block keeps its
+own --no-* switch there).
 
 Workload = the configuration BASELINE.json's metric is quoted on (configs[3] shape): a 3 Gbp 5-haplotype bubble graph in 24
 chromosomes and 125 000 x 10 kb synthetic ONT reads PER GPU (1 M reads at 8 GPUs), `-cx lr -c`.
@@ -20,7 +25,7 @@ order inside the timed region.  Extra keys: `resident` (the same rea
 Graph chaining + the gap list run on the host threads or on the device (the library picks by the host threads a rank has): `value` is the library's choice,
 `device_placement` / `host_placement` is the other one, timed the same way right after it, both compared byte for byte with the reference on every read of the sample.
 
-N = 1 also runs, after the headline, the other BASELINE configurations at their sizes, each compared byte for byte with the reference on the same box: `file_out` (the headline's step with the
+N = 1 with --full also runs, after the headline, the other BASELINE configurations at their sizes, each compared byte for byte with the reference on the same box: `file_out` (the headline's step with the
 GAF written to a file, the interval of the CPU leg), `linear` / `bubble50` (configs[1] / configs[2]: 100 000 reads vs the 50 Mbp linear FASTA / 3-haplotype graph) and `asm`
 (configs[4] at one GPU's share: -cx asm, one ~98 Mbp contig per chromosome vs the 3 Gbp graph, then --call through the reference's own caller).
 
@@ -37,6 +42,7 @@ import sys
 import tempfile
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -201,6 +207,49 @@ def small_configs_block(mga, d, threads, ref_bin, n_reads, genome):
     return res
 
 
+DUMP_BLOCK = 4096            # bytes of the text per entry of gaf_block_sums
+DUMP_SAMPLE_RUN = 65536      # bytes per sampled run of the text
+DUMP_SAMPLE_BYTES = 12 << 20  # sampled bytes in all (float32: 48 MB; the sums of a ~1.1 GB text add 2 MB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, text):
+    """--dump-outputs: the GAF text the last timed step handed to its caller (a uint8 array: the order of the input reads, so the same bytes from run to run -- the
+    workload is generated from fixed seeds) as .npy files of at most 64 MB in all:
+      gaf_size.npy            float64 [bytes, lines]
+      gaf_block_sums.npy      float64, one per 4 KiB block of the WHOLE text: the sum of the block's little-endian 32-bit words (< 2^42: exact), the last block zero-padded
+                              (blocks double in size until there are at most 2^20 of them: gaf_block_bytes.npy)
+      gaf_sample.npy          float32: the bytes of runs of 64 KiB at gaf_sample_offsets.npy (float64), drawn once from a fixed seed (the whole text when it is <= 12 MiB)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(text.size)
+    blk = DUMP_BLOCK
+    while (n + blk - 1) // blk > (1 << 20):
+        blk *= 2
+    nb = (n + blk - 1) // blk
+    sums, lines = np.zeros(nb, dtype=np.float64), 0
+    per = max(1, (64 << 20) // blk)   # blocks per pass of the loop (64 MiB of text at a time)
+    for b0 in range(0, n // blk, per):
+        b1 = min(n // blk, b0 + per)
+        piece = text[b0 * blk:b1 * blk]
+        lines += int(np.count_nonzero(piece == 10))
+        sums[b0:b1] = np.ascontiguousarray(piece).view("<u4").reshape(b1 - b0, blk // 4).sum(axis=1, dtype=np.uint64)
+    if n % blk:
+        tail = np.zeros(blk, dtype=np.uint8)
+        tail[:n % blk] = text[n - n % blk:]
+        lines += int(np.count_nonzero(tail == 10))
+        sums[nb - 1] = tail.view("<u4").sum(dtype=np.uint64)
+    n_run = (n + DUMP_SAMPLE_RUN - 1) // DUMP_SAMPLE_RUN
+    k = DUMP_SAMPLE_BYTES // DUMP_SAMPLE_RUN
+    runs = np.arange(n_run) if n_run <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(n_run, size=k, replace=False))
+    offs = runs.astype(np.int64) * DUMP_SAMPLE_RUN
+    sample = np.concatenate([text[o:min(n, o + DUMP_SAMPLE_RUN)] for o in offs]).astype(np.float32) if n else np.zeros(0, dtype=np.float32)
+    for name, arr in (("gaf_size", np.array([n, lines], dtype=np.float64)), ("gaf_block_bytes", np.array([blk], dtype=np.float64)), ("gaf_block_sums", sums),
+                      ("gaf_sample_offsets", offs.astype(np.float64)), ("gaf_sample", sample)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return dict(dir=out_dir, gaf_bytes=n, gaf_lines=lines, files=["gaf_size", "gaf_block_bytes", "gaf_block_sums", "gaf_sample_offsets", "gaf_sample"])
+
+
 def usable_cores():
     """cores this process may actually burn: the affinity mask capped by the cgroup CPU quota (cpu.max)"""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -256,7 +305,16 @@ def main():
     ap.add_argument("--no-rank-share", action="store_true", help="N=1: skip the `rank_share` block (device placement with the process pinned to 1/8 of the usable cores)")
     ap.add_argument("--share", type=int, default=8, help="rank_share: the node's ranks the usable cores are divided among")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1: nccl (= RCCL over xGMI, the default) or gloo (host tensors: lets one GPU box run 2 ranks on the same device to test the sharded path)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures or checks: the other placement of graph chaining, rank_share, file_out, resident + the isolated passes "
+                                                        "(per-kernel roofline), cpu_baseline + parity with the reference, linear / bubble50 / asm (each still has its own --no-* switch); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the LAST timed step returned to its caller (the GAF text) as DIR/<name>.npy (float32 / float64, "
+                                                                        "at most 64 MB in all: its size, a sum per 4 KiB block of the whole text, a fixed seeded sample of its bytes)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run: set up, warm up, time the steps, (dump,) print -- every other block is off
+        args.no_cpu = args.one_placement = args.no_asm = args.no_small = args.no_file_out = args.no_rank_share = True
+        args.resident_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` launches its own ranks: one process per GPU under torch.distributed.run (the plain command ran ONE rank and said n_gpus 1)
@@ -278,30 +336,11 @@ def main():
     n_gpus = world
     os.environ.setdefault("MGA_DEVICE", str(local_rank))
 
-    import torch
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        if args.backend == "nccl":
-            torch.cuda.set_device(local_rank)
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-        else:
-            torch.cuda.set_device(local_rank % torch.cuda.device_count())
-            dist.init_process_group(args.backend)
-
-    coll_dev = "cuda" if args.backend == "nccl" else "cpu"
-    import minigraph_amd as mga
-    from minigraph_amd.dist import map_sharded
-    L = mga.load()
-    if L.mga_device_count() <= 0:
-        raise SystemExit("bench.py needs an MI355X: no HIP device visible (there is no CPU fallback)")
-    ncpu = os.cpu_count() or 1
-    quota = usable_cores()
-    threads = args.threads or max(2, min(64, quota // world))  # [measured] more threads than usable cores only adds contention + CFS throttling
-
-    # ---- synthetic workload (untimed): ONE graph + ONE read file for the whole job, written by rank 0 ----
+    # ---- synthetic workload (untimed): ONE graph + ONE read file for the whole job, written by rank 0; the generator is started first and runs while torch is
+    #      imported and the process group and the library come up (a single-threaded job of about 10 s next to several seconds of start-up) ----
+    import minigraph_amd as mga   # (the Python side only: the library itself is loaded below, after torch, as before)
     wl_tag = "G%d_c%d_H%d_n%d" % (args.genome, args.chr, args.hap, args.reads * world)
-    reuse_wl = False
+    reuse_wl, gen, d = False, None, None
     if rank == 0:
         if args.workdir:
             d = os.path.join(os.path.abspath(args.workdir), wl_tag)
@@ -309,49 +348,92 @@ def main():
             reuse_wl = os.path.exists(os.path.join(d, "w.done"))
         else:
             d = tempfile.mkdtemp(prefix="mga_bench_")
-        t0 = time.time()
-        if reuse_wl:
-            err_txt = open(os.path.join(d, "w.done")).read()
-        else:
-            p = subprocess.run([mga.MGSIM, "-p", os.path.join(d, "w"), "-G", str(args.genome), "-c", str(args.chr), "-H", str(args.hap),
-                                "-n", str(args.reads * world), "-s", "11"], stderr=subprocess.PIPE, check=True)
-            err_txt = p.stderr.decode()
+        t0_gen = time.time()
+        if not reuse_wl:
+            gen = subprocess.Popen([mga.MGSIM, "-p", os.path.join(d, "w"), "-G", str(args.genome), "-c", str(args.chr), "-H", str(args.hap),
+                                    "-n", str(args.reads * world), "-s", "11", "-L"], stderr=subprocess.PIPE)   # (-L: the backbone as a linear FASTA is not needed here)
+
+    try:
+        import torch
+        dist = None
+        if world > 1:
+            import torch.distributed as dist
+            if args.backend == "nccl":
+                torch.cuda.set_device(local_rank)
+                dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+            else:
+                torch.cuda.set_device(local_rank % torch.cuda.device_count())
+                dist.init_process_group(args.backend)
+
+        coll_dev = "cuda" if args.backend == "nccl" else "cpu"
+        from minigraph_amd.dist import map_sharded
+        L = mga.load()
+        if L.mga_device_count() <= 0:
+            raise SystemExit("bench.py needs an MI355X: no HIP device visible (there is no CPU fallback)")
+    except BaseException:   # nothing is left behind: neither the generator nor its files
+        if gen is not None:
+            gen.kill()
+            gen.wait()
+        if d is not None and not args.workdir:
+            shutil.rmtree(d, ignore_errors=True)
+        raise
+    ncpu = os.cpu_count() or 1
+    quota = usable_cores()
+    threads = args.threads or max(2, min(64, quota // world))  # [measured] more threads than usable cores only adds contention + CFS throttling
+
+    # graph -> index: rank 0 parses the GFA text once (gfa_read + mg_index: `index_build_s`) and writes the graph as ONE binary image; every rank then maps the image
+    # and lets its GPU rebuild the minimizer table (`index_s`: what a run on an existing image pays -- SURVEY 8 f4, csrc/image.c).  The generator writes the graph
+    # first and says so, then the reads: the index is built from the finished GFA file while the reads are still being written.
+    t_build = t_save = t_gen = 0.0
+    graph_bp = 0
+    if rank == 0:
+        img_path = os.path.join(d, "w.mgi")
+        err_txt = open(os.path.join(d, "w.done")).read() if reuse_wl else ""
+        try:
+            while gen is not None:   # up to the generator's "graph written" line (or the end of its output, when it failed)
+                line = gen.stderr.readline().decode()
+                err_txt += line
+                if not line or "graph written" in line:
+                    break
+            if gen is not None and gen.poll() not in (None, 0):
+                raise RuntimeError("the workload generator failed (exit code %d): %s" % (gen.returncode, err_txt[-500:]))
+            if not (reuse_wl and os.path.exists(img_path)):
+                t0 = time.time()
+                G0 = mga.Graph(os.path.join(d, "w.gfa"), preset="lr", cigar=True, n_threads=threads)
+                t_build = time.time() - t0
+                t0 = time.time()
+                G0.save_image(img_path)
+                t_save = time.time() - t0
+                G0.close()
+            if gen is not None:
+                err_txt += gen.communicate()[1].decode()
+                if gen.returncode != 0:
+                    raise RuntimeError("the workload generator failed (exit code %d): %s" % (gen.returncode, err_txt[-500:]))
+        except BaseException:
+            if gen is not None:
+                gen.kill()
+                gen.wait()
+            if not args.workdir:
+                shutil.rmtree(d, ignore_errors=True)
+            raise
+        t_gen = time.time() - t0_gen
+        if args.workdir and not reuse_wl:
+            with open(os.path.join(d, "w.done"), "w") as fo:
+                fo.write(err_txt)
         m = re.search(r"graph=(\d+) bp", err_txt)
         graph_bp = int(m.group(1)) if m else int(args.genome * (1 + 0.071 * (args.hap - 1)))
-        try:
-            os.remove(os.path.join(d, "w.lin.fa"))
-        except OSError:
-            pass
-        t_gen = time.time() - t0
-    else:
-        d, t_gen, graph_bp = None, 0.0, 0
     if dist is not None:
         box = [d]
         dist.broadcast_object_list(box, src=0)
         d = box[0]
     pre = os.path.join(d, "w")
-    graph_path, reads_path = pre + ".gfa", pre + ".reads.fa"
-    # graph -> index: rank 0 parses the GFA text once (gfa_read + mg_index: `index_build_s`) and writes the graph as ONE binary image; every rank then maps the image
-    # and lets its GPU rebuild the minimizer table (`index_s`: what a run on an existing image pays -- SURVEY 8 f4, csrc/image.c)
-    img_path = pre + ".mgi"
-    t_build = t_save = 0.0
-    if rank == 0 and not (reuse_wl and os.path.exists(img_path)):
-        t0 = time.time()
-        G0 = mga.Graph(graph_path, preset="lr", cigar=True, n_threads=threads)
-        t_build = time.time() - t0
-        t0 = time.time()
-        G0.save_image(img_path)
-        t_save = time.time() - t0
-        G0.close()
-        if args.workdir:
-            with open(os.path.join(d, "w.done"), "w") as fo:
-                fo.write(err_txt)
+    graph_path, reads_path, img_path = pre + ".gfa", pre + ".reads.fa", pre + ".mgi"
     if dist is not None:
         dist.barrier()
     t0 = time.time()
     G = mga.Graph(img_path, preset="lr", cigar=True, n_threads=threads, image=True)
     t_index = time.time() - t0
-    log("[bench] rank %d: gen %.1fs, GFA text -> index %.1fs, image written in %.1fs, image -> index %.2fs, %d host threads" % (rank, t_gen, t_build, t_save, t_index, threads))
+    log("[bench] rank %d: workload ready %.1fs after the generator's start (GFA text -> index %.1fs and image written in %.1fs meanwhile), image -> index %.2fs, %d host threads" % (rank, t_gen, t_build, t_save, t_index, threads))
 
     last = {}
 
@@ -417,7 +499,15 @@ def main():
     if args.placement != "auto":
         os.environ["MGA_DEV_GCHAIN"] = "1" if default_dev else "0"
     dt, st, host_main = timed(args.warmup, args.steps)
-    gaf_main = last_gaf()
+    dumped = None
+    if args.dump_outputs and rank == 0:   # what the last timed step returned: the buffer itself (N > 1: the text gathered to rank 0, or rank 0's shard under --no-gather)
+        t0 = time.time()
+        if last.get("gaf_bytes") is not None:
+            dumped = dump_outputs(args.dump_outputs, last["gaf_bytes"].cpu().numpy())
+        else:
+            dumped = dump_outputs(args.dump_outputs, last["gaf"].view())
+        log("[bench] %d timed steps in %.2fs; outputs of the last one written to %s in %.2fs" % (args.steps, dt, args.dump_outputs, time.time() - t0))
+    gaf_main = None if args.no_cpu else last_gaf()   # (a copy of the text for the comparison with the reference: a run without it makes none)
     gfx_block = None
     if args.gfx_activity and dist is None:
         import re as _re
@@ -775,7 +865,10 @@ def main():
                 res["cpu_baseline"] = dict(value=None, unit="Gbp/s", cores=quota, kind="reference", sample="failed: %r" % (e,))
         else:
             res["cpu_baseline"] = dict(value=None, unit="Gbp/s", cores=quota, kind="reference",
-                                       sample="not run (--no-cpu, or oracle/_ref/minigraph absent)")
+                                       sample="not run (a run without --full, --no-cpu, or oracle/_ref/minigraph absent)")
+        res["full"] = bool(args.full)
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if file_out is not None:
             file_out.pop("path", None)
             res["file_out"] = file_out
@@ -818,6 +911,8 @@ def main():
         shutil.rmtree(d, ignore_errors=True)
     if dist is not None:
         dist.destroy_process_group()
+    if rank == 0:
+        log("[bench] %.1fs since the interpreter read this file, %.1fs of them in the %d + %d headline steps at ms_per_step" % (time.time() - T_START, (args.steps + args.warmup) * dt / args.steps, args.warmup, args.steps))
 
 
 if __name__ == "__main__":

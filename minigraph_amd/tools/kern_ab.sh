@@ -1,7 +1,7 @@
 #!/bin/bash
 # isolated per-kernel times of the bench workload under a set of environment knobs:  kern_ab.sh <tag> [ENV=VALUE ...]
 tag=$1; shift
-B="python bench.py --steps 2 --warmup 1 --no-cpu --resident-steps 1 --one-placement --no-asm --no-small --no-file-out --no-rank-share"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu --resident-steps 1 --one-placement --no-asm --no-small --no-file-out --no-rank-share"
 env "$@" $B > gpurun_out/${tag}.json 2> gpurun_out/${tag}.err
 python - <<P
 import json; d=json.load(open("gpurun_out/${tag}.json")); k=d["kernels_ms_isolated"]

@@ -4,7 +4,7 @@
 ulimit -c 0
 for s in "$@"; do
 	[ "$s" = "-" ] && s=""
-	out=$(env $s python bench.py --steps ${STEPS:-4} --warmup 1 --one-placement --no-cpu --resident-steps ${RESIDENT:-0} ${BENCH_ARGS:-} 2>/dev/null | tail -1)
+	out=$(env $s python bench.py --full --steps ${STEPS:-4} --warmup 1 --one-placement --no-cpu --resident-steps ${RESIDENT:-0} ${BENCH_ARGS:-} 2>/dev/null | tail -1)
 	python - "$s" "$out" <<'PY'
 import json, sys
 try:

@@ -2,10 +2,10 @@
  * mgsim -- deterministic synthetic workload generator for the mapping benchmark.
  *
  *   mgsim -p PREFIX [-G backbone_bp] [-c n_chr] [-H n_hap] [-n n_reads] [-l read_len]
- *         [-e err] [-s seed] [-S read_seed] [-R]
+ *         [-e err] [-s seed] [-S read_seed] [-R] [-L]
  *
  * writes
- *   PREFIX.lin.fa    backbone "chromosomes" as FASTA (config: linear reference, no graph)
+ *   PREFIX.lin.fa    backbone "chromosomes" as FASTA (config: linear reference, no graph); not with -L
  *   PREFIX.gfa       rGFA bubble graph: stems + per-bubble ref allele (rank 0) and one alt
  *                    allele per extra haplotype (rank h), SN/SO/SR tags, 0M links with SR
  *   PREFIX.reads.fa  reads sampled uniformly from the haplotype walks, 50% reverse-complemented,
@@ -68,14 +68,14 @@ int main(int argc, char *argv[])
 	int n_chr = 1, H = 3, c, h;
 	double err = 0.10;
 	uint64_t seed = 11, read_seed = 0;
-	int reads_only = 0;
+	int reads_only = 0, no_lin = 0;
 	const char *prefix = 0;
 	char fn[4096];
 	FILE *fgfa, *flin, *frd;
 	str_t *hap; /* hap[h*n_chr + c] */
 	int64_t seg_id = 0, tot_graph = 0, n_bub = 0;
 
-	while ((c = getopt(argc, argv, "p:G:c:H:n:l:e:s:S:R")) >= 0) {
+	while ((c = getopt(argc, argv, "p:G:c:H:n:l:e:s:S:RL")) >= 0) {
 		if (c == 'p') prefix = optarg;
 		else if (c == 'G') G = atoll(optarg);
 		else if (c == 'c') n_chr = atoi(optarg);
@@ -86,14 +86,15 @@ int main(int argc, char *argv[])
 		else if (c == 's') seed = strtoull(optarg, 0, 10);
 		else if (c == 'S') read_seed = strtoull(optarg, 0, 10);
 		else if (c == 'R') reads_only = 1; /* the graph of (-G -c -H -s) exists already: write PREFIX.reads.fa only (more reads / other reads, with -S, against one graph) */
+		else if (c == 'L') no_lin = 1; /* no PREFIX.lin.fa (a job that maps against the graph only: the other two files are the same bytes) */
 	}
 	if (prefix == 0 || H < 1 || n_chr < 1) {
-		fprintf(stderr, "Usage: mgsim -p PREFIX [-G bp=2000000] [-c n_chr=1] [-H n_hap=3] [-n n_reads=1000] [-l read_len=10000] [-e err=0.1] [-s seed=11] [-S read_seed] [-R (reads only)]\n");
+		fprintf(stderr, "Usage: mgsim -p PREFIX [-G bp=2000000] [-c n_chr=1] [-H n_hap=3] [-n n_reads=1000] [-l read_len=10000] [-e err=0.1] [-s seed=11] [-S read_seed] [-R (reads only)] [-L (no PREFIX.lin.fa)]\n");
 		return 1;
 	}
 	rng_seed(seed);
 	snprintf(fn, sizeof fn, "%s.gfa", prefix);      fgfa = fopen(reads_only ? "/dev/null" : fn, "w");
-	snprintf(fn, sizeof fn, "%s.lin.fa", prefix);   flin = fopen(reads_only ? "/dev/null" : fn, "w");
+	snprintf(fn, sizeof fn, "%s.lin.fa", prefix);   flin = fopen(reads_only || no_lin ? "/dev/null" : fn, "w");
 	snprintf(fn, sizeof fn, "%s.reads.fa", prefix); frd  = fopen(fn, "w");
 	if (!fgfa || !flin || !frd) { perror("fopen"); return 1; }
 	hap = (str_t*)calloc((size_t)H * n_chr, sizeof(str_t));
@@ -156,6 +157,7 @@ int main(int argc, char *argv[])
 		free(bb); free(alt); free(hoff);
 	}
 	fclose(fgfa); fclose(flin);
+	fprintf(stderr, "[mgsim] graph written\n"); /* PREFIX.gfa (and PREFIX.lin.fa) are complete: a caller may read them while the reads are drawn */
 
 	/* reads (optionally from their own stream, so that ranks share one graph but draw different reads) */
 	if (read_seed) rng_seed(read_seed);

@@ -582,7 +582,7 @@ def test_bench_launches_its_own_ranks(ranks, reads):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--backend", "gloo", "--reads", str(reads), "--genome", "30000000", "--chr", "2",
-                        "--steps", "1", "--warmup", "1", "--cpu-reads", "6000", "--resident-steps", "0", "--one-placement", "--threads", "4"],
+                        "--full", "--steps", "1", "--warmup", "1", "--cpu-reads", "6000", "--resident-steps", "0", "--one-placement", "--threads", "4"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1]
