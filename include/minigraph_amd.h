@@ -371,6 +371,22 @@ int mga_gaf_div_batch(int n, const float *div, char *out);
 int mga_wfa_batch(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off,
 				  int32_t **score, uint32_t **cigar, int64_t **cig_off);
 
+/* mwf_wfa_exact's low-memory mode (mwf_wfa_seg + mwf_wfa_core with checkpoints, miniwfa.c:440-601,413-416) on the device: the rung a stretch of the chained fallback
+ * reaches when it outgrows the last HBM tier (1 M diagonals / 32 GiB of traceback).  Same shape as mga_wfa_batch, but every problem runs through this rung alone, with a
+ * snapshot every `step` scores (0: MGA_WFA_SEG_STEP, else the step that needs the least memory); score and CIGAR equal mga_wfa_batch's for every step.
+ * The size of a gap is bounded by device memory alone: mga_wfa_seg_bytes(tl, ql, step) is the workspace one problem reserves, with W = tl + ql + 1 diagonals,
+ * B(s) = min(W, 2 s + 1) the widest band at score s, S = min(2 o2 + e2 (tl + ql), x min(tl, ql) + cheaper gap of |tl - ql|) the score bound, n = floor(S / step) snapshots:
+ *   12 (S + 1)  rows of the traceback  + 340 B(S) x 2  value ring and origin ring  + 4 (W + 1)  CIGAR  + 160 n  snapshot headers and checkpoints
+ *   + 20 sum_{j < n} sum_{s = (j+1) step - 17 .. (j+1) step - 1, s >= 0} B(s)  snapshots
+ *   + 1 + sum_{s = 1 .. S} T(s)  traceback of the second pass, T(s) = B(s) for s < step or step < 17, else min(B(s), 2 (s mod step + 17) + 1)
+ * rounded up to 256 bytes (-1: tl or ql not positive, or beyond the rung's 32-bit indices).  mga_wfa_seg_step: the step the host would choose.
+ * mga_wfa_seg_stats: problems this rung solved and snapshots it took since the last reset (a workload that never reaches the ceiling reads 0). */
+int mga_wfa_seg_batch(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off, int32_t step,
+					  int32_t **score, uint32_t **cigar, int64_t **cig_off);
+int64_t mga_wfa_seg_bytes(int32_t tl, int32_t ql, int32_t step);
+int32_t mga_wfa_seg_step(int32_t tl, int32_t ql);
+void mga_wfa_seg_stats(int64_t *problems, int64_t *snapshots, int reset);
+
 #ifdef __cplusplus
 }
 #endif

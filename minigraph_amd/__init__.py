@@ -86,6 +86,13 @@ def load():
     L.mga_last_error.restype = C.c_char_p
     L.mga_sketch_batch.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, pp, pp]
     L.mga_wfa_batch.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, pp, pp, pp]
+    L.mga_wfa_seg_batch.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, pp, pp, pp]
+    L.mga_wfa_seg_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mga_wfa_seg_bytes.restype = C.c_int64
+    L.mga_wfa_seg_step.argtypes = [C.c_int32, C.c_int32]
+    L.mga_wfa_seg_step.restype = C.c_int32
+    L.mga_wfa_seg_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+    L.mga_wfa_seg_stats.restype = None
     L.gfa_read.argtypes = [C.c_char_p]
     L.gfa_read.restype = C.c_void_p
     L.gfa_destroy.argtypes = [C.c_void_p]
@@ -156,12 +163,43 @@ def sketch_batch(seqs, w, k, rid=None):
 
 def wfa_batch(targets, queries):
     """exact miniwfa alignment of n (target, query) pairs -> (scores, list of uint32 cigar arrays)."""
+    return _wfa_batch(targets, queries, None)
+
+
+def wfa_seg_batch(targets, queries, step=0):
+    """the same alignments through the low-memory rung alone (k_wfa_seg.hip: a snapshot every `step` scores, then a second pass whose
+    band restarts at the checkpoints); step 0: the host's choice.  Score and CIGAR equal wfa_batch's for every step."""
+    return _wfa_batch(targets, queries, int(step))
+
+
+def wfa_seg_stats(reset=False):
+    """problems the low-memory rung solved and snapshots it took since the last reset"""
+    p, s = C.c_int64(0), C.c_int64(0)
+    load().mga_wfa_seg_stats(C.byref(p), C.byref(s), 1 if reset else 0)
+    return {"problems": p.value, "snapshots": s.value}
+
+
+def wfa_seg_bytes(tl, ql, step=0):
+    """workspace in bytes the low-memory rung reserves for one tl x ql problem (formula: include/minigraph_amd.h); no GPU involved"""
+    return int(load().mga_wfa_seg_bytes(tl, ql, step))
+
+
+def wfa_seg_step(tl, ql):
+    """the snapshot distance the host chooses for a tl x ql problem (MGA_WFA_SEG_STEP, else the one of least memory)"""
+    return int(load().mga_wfa_seg_step(tl, ql))
+
+
+def _wfa_batch(targets, queries, seg_step):
     L = load()
     tb, to = concat(targets)
     qb, qo = concat(queries)
     sc, cg, co = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    _check(L.mga_wfa_batch(len(targets), tb, to.ctypes.data, qb, qo.ctypes.data, C.byref(sc), C.byref(cg), C.byref(co)),
-           "mga_wfa_batch")
+    if seg_step is None:
+        _check(L.mga_wfa_batch(len(targets), tb, to.ctypes.data, qb, qo.ctypes.data, C.byref(sc), C.byref(cg), C.byref(co)),
+               "mga_wfa_batch")
+    else:
+        _check(L.mga_wfa_seg_batch(len(targets), tb, to.ctypes.data, qb, qo.ctypes.data, seg_step, C.byref(sc), C.byref(cg), C.byref(co)),
+               "mga_wfa_seg_batch")
     n = len(targets)
     o = _take(co, n + 1, np.int64)
     s = _take(sc, n, np.int32)

@@ -20,6 +20,7 @@
 //   cig   uint32 [CIGCAP]    CIGAR built back-to-front during traceback
 // Three capacity tiers (WMAX/TBCAP/SMAX/CIGCAP); a problem that does not fit is handed to the
 // next tier by the host driver (status MGA_WFA_RETRY_TIER).  Nothing falls back to the CPU.
+#include <stdlib.h>
 #include "mga_dev.h"
 #include "dev_common.h"
 
@@ -308,7 +309,8 @@ static const wfa_cfg_t g_tier[3] = {
 	// the sub-problems of the chained fallback have no cell cap (miniwfa.c:831): last tier for them -- round 5: a million diagonals and 32 GiB of traceback for ONE problem at a
 	// time (allocated when a stretch first gets here: 33 GB of the 288), where rounds 1-4 stopped at 131 072 diagonals / 4 GiB.  The reference bounds the memory of such a stretch
 	// instead (mwf_wfa_seg, miniwfa.c:440-601: checkpoints every 5000 scores, then a second pass whose band restarts at each checkpoint) and arrives at the same CIGAR (DESIGN 4,
-	// chained fallback); a stretch beyond THIS tier -- two unrelated sequences of ~180 kb each without a shared 13-mer chain between them -- still fails loudly.
+	// chained fallback); a stretch beyond THIS tier goes on to that low-memory mode on the device (k_wfa_seg.hip, run by the scheduler after the sweep), whose limit is device
+	// memory by the formula of mga_wfa_seg_bytes().  MGA_WFA_LAST_WMAX / MGA_WFA_LAST_TBCAP lower this tier's capacity (tests: small inputs then take that route).
 	{ 4, 4, 2, 15, 1, 1 << 20, 1 << 20, 1 << 22, 32LL << 30,  -1,        0 },
 };
 static const int g_tier_waves[3] = { 256, 16, 1 };
@@ -322,6 +324,14 @@ extern "C" int mga_dev_wfa(mga_sctx_t *sc, const int *d_n, int n, int first, int
 	if (sc->wfa_uncapped) tier = tier == 1 ? 2 : tier; // ladder of the fallback's sub-problems: same first HBM tier, then the unbounded one
 	wfa_cfg_t cfg = g_tier[tier];
 	if (sc->wfa_uncapped) cfg.max_iter = -1;
+	if (tier == 2) { // (only the uncapped ladder has this tier, and there the low-memory rung catches what falls off it.)  Read at every call: a test sets and unsets them within one process
+		const char *e = getenv("MGA_WFA_LAST_WMAX");
+		const long long w = e ? atoll(e) : 0;
+		if (w > 0 && w < cfg.wmax) cfg.wmax = (int32_t)w;
+		e = getenv("MGA_WFA_LAST_TBCAP");
+		const long long c = e ? atoll(e) : 0;
+		if (c > 0 && c < cfg.tbcap) cfg.tbcap = c;
+	}
 	cfg.ws_stride = (int64_t)wfa_ws_bytes(cfg);
 	int waves = g_tier_waves[tier];
 	if (waves > n - first) waves = n - first;

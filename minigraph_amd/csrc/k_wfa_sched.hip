@@ -347,6 +347,30 @@ extern "C" void mga_wfa_ladder_stats(int64_t *launched, int64_t *given_up, int r
 	}
 }
 
+// The rung behind the ladder (k_wfa_seg.hip): the stretches of the chained fallback that outgrew the last HBM tier are closed in the reference's low-memory mode
+// (miniwfa.c:440-601), whose memory the host sizes per problem.  They are the problems a finished sweep leaves with MGA_WFA_RETRY_TIER; a handful at most, so the
+// host reads their descriptors back in one copy.  What cannot be placed even there fails with the computed figure (mga_dev_wfa_seg).
+static int wfs_seg_rung(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap,
+						unsigned long long *d_pool_used, int *d_cnt /* two free words of the control block */)
+{
+	hipStream_t st = (hipStream_t)sc->stream;
+	int k = 0;
+	if (mga_dbuf_reserve(&sc->wfa_list[1], (size_t)n * 4 + 64) < 0) return -1;
+	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
+	hipLaunchKernelGGL(k_wfa_collect_open, dim3((n + 255) / 256), dim3(256), 0, st, n, (const mga_wfa_res_t*)d_res, (int32_t*)sc->wfa_list[1].p, d_cnt);
+	MGA_HIP_CHECK(hipGetLastError());
+	if (mga_d2h_s(sc, &k, d_cnt, 4) < 0 || mga_ssync(sc) < 0) return -1;
+	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
+	if (k <= 0) return 0;
+	std::vector<int32_t> ids((size_t)k), tl((size_t)k), ql((size_t)k);
+	if (mga_d2h(ids.data(), sc->wfa_list[1].p, (size_t)k * 4) < 0) return -1;
+	std::sort(ids.begin(), ids.end()); // (collected in completion order; the pool's layout should not depend on it)
+	std::vector<mga_wfa_prob_t> pb((size_t)(ids[k - 1] - ids[0] + 1)); // the uncapped ladder's problems are the few stretches of a fallback: one copy of the span that holds them
+	if (mga_d2h(pb.data(), d_prob + ids[0], pb.size() * sizeof(mga_wfa_prob_t)) < 0) return -1;
+	for (int j = 0; j < k; ++j) tl[j] = pb[ids[j] - ids[0]].tl, ql[j] = pb[ids[j] - ids[0]].ql;
+	return mga_dev_wfa_seg(sc, k, ids.data(), tl.data(), ql.data(), 0, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used);
+}
+
 // One SWEEP of the ladder (round 3): the rungs run ONCE each, in ascending order, on the context's stream.  A problem that gives up on rung t is appended to
 // the list of a HIGHER rung, which has not started yet and reads its list's length from device memory when it does -- so every retry is served in the same
 // sweep, with no host round trip between the rungs (round 2 ran pass after pass, every rung again for the problems that had climbed to it: seven host
@@ -355,7 +379,7 @@ extern "C" void mga_wfa_ladder_stats(int64_t *launched, int64_t *given_up, int r
 // the host then sweeps once more over what is still open.
 static int wfs_sweep(mga_sctx_t *sc, const wfs_ladder_t *LD, int arr_pct, int n_list, const int32_t *d_ids /* NULL: problems 0 .. n_list - 1 */,
 					 const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap,
-					 unsigned long long *d_pool_used, int *ctl, bool *any_tb, int *n_open)
+					 unsigned long long *d_pool_used, int *ctl, bool *any_tb, int *n_open, int *n_over /* problems that fell off the last rung (uncapped ladder only: elsewhere an error) */)
 {
 	constexpr int NS = MGA_WFA_N_SLOT;
 	constexpr int O_TOFF = WFS_NBIN, O_RC = O_TOFF + 16, O_ERR = O_RC + 32;
@@ -476,7 +500,10 @@ static int wfs_sweep(mga_sctx_t *sc, const wfs_ladder_t *LD, int arr_pct, int n_
 		fprintf(stderr, "\n");
 	}
 	if (herr) { mga_set_error("WFA: %d problems failed (CIGAR pool of %ld ops exhausted, iteration cap, or a traceback walked out of its window)", herr, (long)pool_cap); return -1; }
-	if (hr[15] > 0) { mga_set_error("%d WFA problems exceed the largest capacity tier", hr[15]); return -1; }
+	if (hr[15] > 0) {
+		if (!sc->wfa_uncapped) { mga_set_error("%d WFA problems exceed the largest capacity tier", hr[15]); return -1; }
+		*n_over += hr[15]; // their status is MGA_WFA_RETRY_TIER: the low-memory rung takes them after the sweeps (wfs_seg_rung)
+	}
 	if (!sc->wfa_uncapped) for (int t = 0; t < NR; ++t) {
 		__atomic_fetch_add(&g_rung_n[t], (long long)(hr[t] < cap[t] ? hr[t] : cap[t]), __ATOMIC_RELAXED);
 		__atomic_fetch_add(&g_rung_up[t], (long long)(hr[t] - own[t]), __ATOMIC_RELAXED); // (arrivals AT rung t)
@@ -503,10 +530,10 @@ extern "C" int mga_dev_wfa_solve(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_
 	hipLaunchKernelGGL(k_wfa_mark_pending, dim3((n + 255) / 256), dim3(256), 0, st, n, d_res);
 	MGA_HIP_CHECK(hipGetLastError());
 	bool any_tb = false;
-	int n_open = 0;
+	int n_open = 0, n_over = 0;
 	static int arr_pct = -1;
 	if (arr_pct < 0) { const char *e = getenv("MGA_WFA_ARRIVALS_PCT"); arr_pct = e ? atoi(e) : 20; } // (tests: 0 leaves a rung's list room for 4096 arrivals only)
-	if (wfs_sweep(sc, LD, arr_pct, n, 0, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open) < 0) return -1;
+	if (wfs_sweep(sc, LD, arr_pct, n, 0, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open, &n_over) < 0) return -1;
 	if (n_open > 0) { // a rung's list overflowed (far more of a chunk's gaps gave up than any read set has shown): what is still open is swept again in slices whose
 		// lists have room for EVERYTHING below them (no second overflow), small enough for the traceback regions that implies
 		const int SLICE = 32768;
@@ -518,10 +545,11 @@ extern "C" int mga_dev_wfa_solve(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_
 		if (mga_d2h_s(sc, &k, d_cnt, 4) < 0 || mga_ssync(sc) < 0) return -1;
 		MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
 		for (int o = 0; o < k; o += SLICE) {
-			if (wfs_sweep(sc, LD, 100, k - o < SLICE ? k - o : SLICE, (const int32_t*)sc->wfa_list[1].p + o, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open) < 0) return -1;
+			if (wfs_sweep(sc, LD, 100, k - o < SLICE ? k - o : SLICE, (const int32_t*)sc->wfa_list[1].p + o, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open, &n_over) < 0) return -1;
 			if (n_open > 0) { mga_set_error("WFA ladder: %d problems open after a sweep with room for all", n_open); return -1; }
 		}
 	}
+	if (n_over > 0 && wfs_seg_rung(sc, n, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl + O_CELLS) < 0) return -1;
 	{ // problems the exact pass gave up on (> 1e8 cells): miniwfa's chained fallback (miniwfa.c:829-832)
 		int n_fb = 0;
 		if (mga_d2h_s(sc, &n_fb, ctl + O_FB, 4) < 0 || mga_ssync(sc) < 0) return -1;

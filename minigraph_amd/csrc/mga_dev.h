@@ -54,6 +54,7 @@ typedef struct mga_sctx_s {
 	mga_dbuf_t fb_prob, fb_res; /* sub-problems of the chained fallback and their results */
 	mga_dbuf_t sk_planes; const void *sk_planes_src; /* the packed (bit-plane) form of a read buffer (mga_dev_pack2) and the buffer it was made from: sketch launches on that buffer read it */
 	const int32_t *lc_order;   /* launch order of the NEXT mga_dev_lchain call on this context (device array of n read numbers; consumed by the call) */
+	mga_dbuf_t wfa_seg_ws, wfa_seg_job; /* low-memory WFA rung (k_wfa_seg.hip): workspaces of the problems of one launch, their descriptors and outcomes */
 } mga_sctx_t;
 static inline void mga_dev_lchain_order(mga_sctx_t *sc, const int32_t *d_order) { sc->lc_order = d_order; }
 void *mga_wfa_stream(mga_sctx_t *sc, int slot);       /* stream of WFA tier `slot` (the context's own stream unless MGA_WFA_CONCURRENT=1) */
@@ -176,6 +177,10 @@ typedef struct { int32_t *list; int *cnt; int *err; int32_t *fb_list; int *fb_cn
  * appended to d_pool (capacity pool_cap ops, *d_pool_used bumped atomically); sequences must be padded by >= 8 readable bytes */
 int mga_dev_wfa(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
 				mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt);
+/* the rung behind the last HBM tier (k_wfa_seg.hip): mwf_wfa_exact's low-memory mode, a workgroup per problem.  ids[n] (NULL: 0 .. n-1) index d_prob / d_res; h_tl / h_ql [n]
+ * are those problems' lengths on the host; step 0: the host's choice (MGA_WFA_SEG_STEP, else the step of least memory).  Synchronous; fails with a message when a problem cannot be placed. */
+int mga_dev_wfa_seg(mga_sctx_t *sc, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step, const mga_wfa_prob_t *d_prob,
+					const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used);
 /* register-resident tiers (k_wfa_r.hip): tier 0-2 one wave per problem (64, 128, 192 diagonals), 3-6 two to sixteen waves (256, 512, 1024, 2048) */
 int mga_dev_wfa_reg(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
 					mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt);

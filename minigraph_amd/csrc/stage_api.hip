@@ -74,8 +74,9 @@ extern "C" int mga_sketch_batch(int n, const char *seq, const int64_t *off, cons
 	return 0;
 }
 
-extern "C" int mga_wfa_batch(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off,
-							 int32_t **score, uint32_t **cigar, int64_t **cig_off)
+// seg_step < 0: the ladder (mga_dev_wfa_solve); >= 0: every problem through the low-memory rung alone (k_wfa_seg.hip) at that step (0: the host's choice)
+static int wfa_batch_impl(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off, int seg_step,
+						  int32_t **score, uint32_t **cigar, int64_t **cig_off)
 {
 	*score = 0, *cigar = 0, *cig_off = 0;
 	if (mga_dev_init() < 0) return -1;
@@ -98,7 +99,12 @@ extern "C" int mga_wfa_batch(int n, const char *tseq, const int64_t *t_off, cons
 
 	std::vector<mga_wfa_res_t> res(n);
 	if (!d_pool.alloc((size_t)pool_cap * 4) || mga_dmemset_s(SC, d_used.p, 0, 8) < 0) return -1;
-	if (mga_dev_wfa_solve(SC, n, d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(),
+	if (seg_step >= 0) {
+		std::vector<int32_t> tl(n), ql(n);
+		for (int i = 0; i < n; ++i) tl[i] = prob[i].tl, ql[i] = prob[i].ql;
+		if (mga_dev_wfa_seg(SC, n, 0, tl.data(), ql.data(), seg_step, d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(),
+							d_pool.as<uint32_t>(), pool_cap, (unsigned long long*)d_used.p) < 0) return -1;
+	} else if (mga_dev_wfa_solve(SC, n, d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(),
 						  d_pool.as<uint32_t>(), pool_cap, (unsigned long long*)d_used.p, 0, 0, 0) < 0) return -1;
 	if (mga_dsync() < 0 || mga_d2h(res.data(), d_res.p, (size_t)n * sizeof(mga_wfa_res_t)) < 0) return -1;
 	unsigned long long used = 0;
@@ -116,6 +122,19 @@ extern "C" int mga_wfa_batch(int n, const char *tseq, const int64_t *t_off, cons
 			memcpy(h_cig + h_off[i], hpool.data() + res[i].cig_off, (size_t)res[i].n_cigar * 4);
 	*score = h_score, *cigar = h_cig, *cig_off = h_off;
 	return 0;
+}
+
+extern "C" int mga_wfa_batch(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off,
+							 int32_t **score, uint32_t **cigar, int64_t **cig_off)
+{
+	return wfa_batch_impl(n, tseq, t_off, qseq, q_off, -1, score, cigar, cig_off);
+}
+
+extern "C" int mga_wfa_seg_batch(int n, const char *tseq, const int64_t *t_off, const char *qseq, const int64_t *q_off, int32_t step,
+								 int32_t **score, uint32_t **cigar, int64_t **cig_off)
+{
+	if (step < 0) { mga_set_error("wfa_seg: negative step %d", step); return -1; }
+	return wfa_batch_impl(n, tseq, t_off, qseq, q_off, step, score, cigar, cig_off);
 }
 
 struct mg_idx_bucket_s_view { mga_didx_t dev; }; // first member of the hidden index struct (mga_host.h)
