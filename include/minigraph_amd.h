@@ -282,6 +282,29 @@ int mga_reads_parse_x(const char *fn, int64_t batch_bases, int n_threads, int64_
  * records per output segment.  No device needed. */
 int mga_reads_shard_dump(const char *fn, int64_t batch_bases, int n_threads, int rank, int world, const char *out_path, int64_t **seg_n, int *n_seg);
 
+/* ---- ADDITIVE: read coverage (--cov: gmap.c:115-126,193-208 + cal_cov.c:8-53) as INTEGER sums: seg_bases[g->n_seg] = covered bases per segment, link_cnt[g->n_arc] =
+ * traversals per arc.  Integer sums do not depend on the order of the additions, on chunking or on the number of ranks; the reference's values -- (double)(e - s) / len
+ * per (chain, segment) and 1.0 per link, stored as float -- follow once, at the end (mga_cov_finish).  A chain counts when mapq >= opt->min_cov_mapq && blen >=
+ * opt->min_cov_blen, with the chain record's blen (cal_cov.c:17) whether or not MG_M_CIGAR is set; every chain of a read is tested, secondaries (MAPQ 0) included. ---- */
+typedef struct { int64_t vert_beg; int32_t vert_cnt, ps, pe, plen, mapq, blen; } mga_cov_chain_t; /* one graph chain: its oriented walk vert[vert_beg .. + vert_cnt) and the fields of mg_gchain_t the count reads */
+typedef struct { int64_t chains_counted, links_counted, links_skipped; } mga_cov_stats_t; /* links_skipped: none or several arcs between two walk vertices (the reference's "[W] Multi/disconnected link", verbose >= 2) */
+/* maps this rank's shard of every file (rank 0 of world 1: all of it) and ADDS into the caller's seg_bases / link_cnt / *st (st may be NULL): several calls -- files, ranks --
+ * sum.  The counting runs on the device (k_cov.hip) into accumulators that stay in HBM for the whole call; no GAF is made.  MG_M_FRAG_MODE is refused (-1).  *t_map: as above. */
+int mga_map_files_cov(const mg_idx_t *gi, int n_fn, const char **fn, const mg_mapopt_t *opt, int n_threads, int shard_rank, int shard_world,
+					  int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st, double *t_map);
+/* cov_seg[i] = (double)seg_bases[i] / len(i), cov_link[k] = (double)link_cnt[k]: the arrays the reference hands to gfa_aux_update_cv (either output may be NULL) */
+void mga_cov_finish(const gfa_t *g, const int64_t *seg_bases, const int64_t *link_cnt, double *cov_seg, double *cov_link);
+/* gfa_aux_update_cv (gfa-base.c:475-503) under a name of this library's own, with ALL of its observable behaviour: a line that carries a cv tag gets the 4 bytes behind that
+ * tag's type overwritten with the float; every other line gets `tag`:f: APPENDED, also when it already has one */
+void mga_gfa_aux_update_cv(gfa_t *g, const char *tag, const double *cov_seg, const double *cov_link);
+/* the count alone, on host threads' code path (cov_core.h compiled for the host; no device needed): mg_cov_map over one read's chains / over flat records */
+void mga_cov_gchains(const gfa_t *g, const mg_gchains_t *gt, int32_t min_mapq, int32_t min_blen, int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st);
+void mga_cov_chains_host(const gfa_t *g, int n_chain, const mga_cov_chain_t *chain, const uint32_t *vert, int32_t min_mapq, int32_t min_blen,
+						 int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st);
+/* the same flat records through k_cov.hip against gi's graph replica (stage-level entry: host pointers in and out; adds into the three outputs) */
+int mga_cov_batch(const mg_idx_t *gi, int n_chain, const mga_cov_chain_t *chain, int64_t n_vert, const uint32_t *vert, int32_t min_mapq, int32_t min_blen,
+				  int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st);
+
 /* a read set kept resident in HBM across calls (repeated passes over one batch, as the benchmark does) */
 typedef struct mga_reads_s mga_reads_t;
 mga_reads_t *mga_reads_load(const char *fn, int64_t max_reads);   /* FASTA/FASTQ(.gz) -> host copy + HBM copy; NULL on error */

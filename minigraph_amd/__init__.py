@@ -62,7 +62,7 @@ MG_M_CIGAR = 0x4000000
 
 KERNELS = ["k_sketch", "k_seed_count", "k_seed_fill", "k_lchain", "k_wfa_r[64]", "k_wfa_r[128]", "k_wfa_r[192]", "k_wfa_r[256]", "k_wfa_r[512]",
            "k_wfa_r[1024]", "k_wfa_r[2048]", "k_wfa[hbm4096]", "k_wfa[hbm32768]", "k_scan", "k_text", "k_gchain", "k_plan",
-           "k_wfa_w[16x4]", "k_wfa_w[32x2]", "k_wfa_w[64]", "k_wfa_w[128]", "k_wfa_w[192]", "k_wfa_w[256]", "k_wfa_tb", "k_gchain_p2", "k_gchain_p3", "k_gaf"]
+           "k_wfa_w[16x4]", "k_wfa_w[32x2]", "k_wfa_w[64]", "k_wfa_w[128]", "k_wfa_w[192]", "k_wfa_w[256]", "k_wfa_tb", "k_gchain_p2", "k_gchain_p3", "k_gaf", "k_cov"]
 
 
 class stats_t(C.Structure):  # mga_stats_t
@@ -490,6 +490,95 @@ def map_reads(graph, reads, n_threads=8, copy=True):
     out = gb.bytes()
     gb.free()
     return out
+
+
+class cov_chain_t(C.Structure):  # mga_cov_chain_t
+    _fields_ = [("vert_beg", C.c_int64), ("vert_cnt", C.c_int32), ("ps", C.c_int32), ("pe", C.c_int32), ("plen", C.c_int32),
+                ("mapq", C.c_int32), ("blen", C.c_int32)]
+
+
+class cov_stats_t(C.Structure):  # mga_cov_stats_t
+    _fields_ = [(n, C.c_int64) for n in ("chains_counted", "links_counted", "links_skipped")]
+
+
+cov_chain_dtype = np.dtype([("vert_beg", "<i8"), ("vert_cnt", "<i4"), ("ps", "<i4"), ("pe", "<i4"), ("plen", "<i4"), ("mapq", "<i4"), ("blen", "<i4")])
+
+
+def _cov_sizes(g):
+    """(n_seg, n_arc) of a gfa_t* (gfa_t: m_seg, n_seg, max_rank, seg, h_names, m_sseq, n_sseq, sseq, h_snames, m_arc, n_arc, ...)"""
+    u32 = C.cast(g, C.POINTER(C.c_uint32))
+    u64 = C.cast(g, C.POINTER(C.c_uint64))
+    return int(u32[1]), int(u64[8])
+
+
+def _cov_stats(st):
+    return {k: getattr(st, k) for k, _ in st._fields_}
+
+
+def cov_finish(g, seg_bases, link_cnt):
+    """mga_cov_finish: the doubles the reference hands to gfa_aux_update_cv, from the integer sums"""
+    L = load()
+    cs, cl = np.zeros(len(seg_bases), dtype=np.float64), np.zeros(len(link_cnt), dtype=np.float64)
+    L.mga_cov_finish.argtypes = [C.c_void_p] * 5
+    L.mga_cov_finish.restype = None
+    L.mga_cov_finish(g, seg_bases.ctypes.data, link_cnt.ctypes.data, cs.ctypes.data, cl.ctypes.data)
+    return cs, cl
+
+
+def map_cov_ints(graph, read_paths, n_threads=8, rank=0, world=1, min_cov_mapq=None, min_cov_blen=None):
+    """mga_map_files_cov: this rank's shard of the files -> (seg_bases, link_cnt, stats, t_map); the two int64 arrays of several ranks / calls simply add"""
+    L = load()
+    n_seg, n_arc = _cov_sizes(graph.g)
+    mo = mapopt_t.from_buffer_copy(graph.mo)
+    if min_cov_mapq is not None:
+        mo.min_cov_mapq = min_cov_mapq
+    if min_cov_blen is not None:
+        mo.min_cov_blen = min_cov_blen
+    fns = (C.c_char_p * len(read_paths))(*[p.encode() for p in read_paths])
+    sb, lc = np.zeros(n_seg, dtype=np.int64), np.zeros(n_arc, dtype=np.int64)
+    st, t = cov_stats_t(), C.c_double(0.0)
+    L.mga_map_files_cov.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(mapopt_t), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.POINTER(cov_stats_t), C.POINTER(C.c_double)]
+    _check(L.mga_map_files_cov(graph.gi, len(read_paths), fns, C.byref(mo), n_threads, rank, world, sb.ctypes.data, lc.ctypes.data, C.byref(st), C.byref(t)),
+           "mga_map_files_cov")
+    return sb, lc, _cov_stats(st), t.value
+
+
+def map_cov(graph, read_paths, n_threads=8, min_cov_mapq=None, min_cov_blen=None):
+    """read coverage of the files on the graph (`minigraph --cov`): (seg_bases, link_cnt, cov_seg, cov_link) -- covered bases per segment and traversals per
+    arc as int64, and the doubles the reference tags the graph with (dc:f: stores them as float)"""
+    sb, lc, _, _ = map_cov_ints(graph, read_paths, n_threads, 0, 1, min_cov_mapq, min_cov_blen)
+    cs, cl = cov_finish(graph.g, sb, lc)
+    return sb, lc, cs, cl
+
+
+def _cov_flat(chains, vert):
+    ch = np.ascontiguousarray(chains, dtype=cov_chain_dtype)
+    v = np.ascontiguousarray(vert, dtype=np.uint32)
+    return ch, v
+
+
+def cov_chains_host(g, chains, vert, min_mapq, min_blen):
+    """the host instantiation of cov_core.h over flat chain records (no GPU): (seg_bases, link_cnt, stats)"""
+    L = load()
+    ch, v = _cov_flat(chains, vert)
+    n_seg, n_arc = _cov_sizes(g)
+    sb, lc, st = np.zeros(n_seg, dtype=np.int64), np.zeros(n_arc, dtype=np.int64), cov_stats_t()
+    L.mga_cov_chains_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(cov_stats_t)]
+    L.mga_cov_chains_host.restype = None
+    L.mga_cov_chains_host(g, len(ch), ch.ctypes.data, v.ctypes.data, min_mapq, min_blen, sb.ctypes.data, lc.ctypes.data, C.byref(st))
+    return sb, lc, _cov_stats(st)
+
+
+def cov_batch(graph, chains, vert, min_mapq, min_blen):
+    """the same records through k_cov.hip against the graph's replica in HBM: (seg_bases, link_cnt, stats)"""
+    L = load()
+    ch, v = _cov_flat(chains, vert)
+    n_seg, n_arc = _cov_sizes(graph.g)
+    sb, lc, st = np.zeros(n_seg, dtype=np.int64), np.zeros(n_arc, dtype=np.int64), cov_stats_t()
+    L.mga_cov_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(cov_stats_t)]
+    _check(L.mga_cov_batch(graph.gi, len(ch), ch.ctypes.data, len(v), v.ctypes.data, min_mapq, min_blen, sb.ctypes.data, lc.ctypes.data, C.byref(st)), "mga_cov_batch")
+    return sb, lc, _cov_stats(st)
 
 
 def get_stats(graph, reset=False):

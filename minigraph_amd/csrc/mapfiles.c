@@ -642,7 +642,7 @@ static void *writer_main(void *a)
 	return 0;
 }
 
-typedef struct { mga_stream_t *S; chan_t *sub, *out, *free_b; volatile int err; char errmsg[512]; } collector_t;
+typedef struct { mga_stream_t *S; chan_t *sub, *out, *free_b; volatile int err; char errmsg[512]; pthread_mutex_t *pool_m; wbuf_t **pool; int *n_pool; /* out == NULL (a coverage job: no text, no writer): the buffers go straight back */ } collector_t;
 static void *collector_main(void *a)
 {
 	collector_t *C = (collector_t*)a;
@@ -655,9 +655,10 @@ static void *collector_main(void *a)
 		if (mg_verbose >= 3 && w->fb) fprintf(stderr, "[M::%s] mapped %d sequences\n", "mg_map_files", w->fb->n);
 		if (w->fb) chan_put(C->free_b, w->fb); /* the batch's memory is free to be parsed into again */
 		w->fb = 0;
-		chan_put(C->out, w);
+		if (C->out) chan_put(C->out, w);
+		else { pthread_mutex_lock(C->pool_m); C->pool[(*C->n_pool)++] = w; pthread_mutex_unlock(C->pool_m); }
 	}
-	chan_put(C->out, 0);
+	if (C->out) chan_put(C->out, 0);
 	return 0;
 }
 
@@ -680,8 +681,33 @@ void mga_idx_mf_free(mg_idx_t *gi)
  * *t_map (optional): seconds from the first byte read to the last byte handed to the sink -- the interval between the reference's
  * mg_opt_update and its last worker_pipeline log line (gmap.c:186-211).  The job runs on the index's own chunk pipeline and keeps its
  * read batches and output buffers with the index, so a second job on the same index allocates nothing. */
+static int map_files_job(const mg_idx_t *gi, int n_fn, const char **fn, const mg_mapopt_t *opt, int n_threads, int shard_rank, int shard_world,
+						 FILE *fp, char **mem, int64_t *mem_len, int64_t *mem_cap, int64_t **seg_len, int *n_seg, double *t_map, mga_cov_job_t *cov);
 int mga_map_files_shard(const mg_idx_t *gi, int n_fn, const char **fn, const mg_mapopt_t *opt, int n_threads, int shard_rank, int shard_world,
 						FILE *fp, char **mem, int64_t *mem_len, int64_t *mem_cap, int64_t **seg_len, int *n_seg, double *t_map)
+{
+	return map_files_job(gi, n_fn, fn, opt, n_threads, shard_rank, shard_world, fp, mem, mem_len, mem_cap, seg_len, n_seg, t_map, 0);
+}
+
+/* --cov: the same job ending in integer accumulators instead of GAF (k_cov.hip): no text is made or copied, no writer thread runs; the accumulators stay in HBM until
+ * the last chunk is through and come down once (mga_cov_job_close), added into the caller's arrays */
+int mga_map_files_cov(const mg_idx_t *gi, int n_fn, const char **fn, const mg_mapopt_t *opt, int n_threads, int shard_rank, int shard_world,
+					  int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st, double *t_map)
+{
+	mga_cov_job_t *J;
+	int ret;
+	if (opt->flag & MG_M_FRAG_MODE) { /* the is_skip branch of cal_cov.c:34-39 and gmap.c:109-118 are about multi-segment fragments: not on this path */
+		mga_set_error("--cov with --frag (multi-segment fragments) is outside the MI355X long-read path");
+		return -1;
+	}
+	if (mga_dev_init() < 0 || (J = mga_cov_job_open(gi, opt)) == 0) return -1;
+	ret = map_files_job(gi, n_fn, fn, opt, n_threads, shard_rank, shard_world, 0, 0, 0, 0, 0, 0, t_map, J);
+	if (mga_cov_job_close(J, ret == 0 ? seg_bases : 0, link_cnt, st) < 0) ret = -1;
+	return ret;
+}
+
+static int map_files_job(const mg_idx_t *gi, int n_fn, const char **fn, const mg_mapopt_t *opt, int n_threads, int shard_rank, int shard_world,
+						 FILE *fp, char **mem, int64_t *mem_len, int64_t *mem_cap, int64_t **seg_len, int *n_seg, double *t_map, mga_cov_job_t *cov)
 {
 	int ret = 0, k, n_sub = 0, n_pool = 0;
 	chan_t c_in, c_free, c_sub, c_out;
@@ -702,8 +728,9 @@ int mga_map_files_shard(const mg_idx_t *gi, int n_fn, const char **fn, const mg_
 		if (sink.mem_cap == 0 && sink.mem) { mga_host_unpin(sink.mem); free(sink.mem); sink.mem = 0; }
 		*mem = 0, *mem_len = 0; sink.to_mem = 1;
 	}
-	if (opt->flag & (MG_M_FRAG_MODE | MG_M_CAL_COV)) { /* gmap.c:44-48,119-126,199-214: multi-segment fragments and --cov are not on the accelerated path */
-		if (mg_verbose >= 1) fprintf(stderr, "[E::%s] --frag and --cov are outside the MI355X long-read path (single-segment reads, GAF output)\n", __func__);
+	if ((opt->flag & MG_M_FRAG_MODE) || ((opt->flag & MG_M_CAL_COV) && cov == 0)) { /* gmap.c:44-48,109-118: multi-segment fragments are not on the accelerated path; a --cov job comes through mga_map_files_cov() */
+		if (mg_verbose >= 1) fprintf(stderr, "[E::%s] --frag is outside the MI355X long-read path (single-segment reads); --cov jobs go through mga_map_files_cov()\n", __func__);
+		mga_set_error("--frag is outside the MI355X long-read path; --cov jobs go through mga_map_files_cov() / mg_map_files()");
 		mga_host_unpin(sink.mem); free(sink.mem);
 		return -1;
 	}
@@ -715,6 +742,7 @@ int mga_map_files_shard(const mg_idx_t *gi, int n_fn, const char **fn, const mg_
 		gi->B->mf_cache = mc;
 	}
 	mc = (mf_cache_t*)gi->B->mf_cache;
+	mga_stream_set_cov(S, cov);
 	if (sink.to_mem && sink.mem == 0) { /* one allocation of about the size of the input for the whole output (a base-aligned read prints ~0.9 bytes per base) */
 		struct stat st;
 		int64_t tot = 0;
@@ -730,10 +758,10 @@ int mga_map_files_shard(const mg_idx_t *gi, int n_fn, const char **fn, const mg_
 	R.n_threads = n_threads < 8 ? n_threads : 8, R.want_pinned = 1, R.rank = shard_rank, R.world = shard_world;
 	R.first_bases = 64000000 < opt->mini_batch_size ? 64000000 : opt->mini_batch_size; /* a short first batch: the GPU starts while the reader is still on the second one */
 	W.sink = &sink, W.in = &c_out, W.pool_m = &pool_m, W.pool = pool, W.n_pool = &n_pool, W.err = 0;
-	C.S = S, C.sub = &c_sub, C.out = &c_out, C.free_b = &c_free, C.err = 0, C.errmsg[0] = 0;
+	C.S = S, C.sub = &c_sub, C.out = cov ? 0 : &c_out, C.free_b = &c_free, C.err = 0, C.errmsg[0] = 0, C.pool_m = &pool_m, C.pool = pool, C.n_pool = &n_pool;
 	pthread_create(&t_rd, 0, reader_main, &R);
 	pthread_create(&t_co, 0, collector_main, &C);
-	pthread_create(&t_wr, 0, writer_main, &W);
+	if (!cov) pthread_create(&t_wr, 0, writer_main, &W);
 	while ((b = (fbatch_t*)chan_get(&c_in)) != 0) {
 		wbuf_t *w = 0;
 		if (C.err || W.err) { chan_put(&c_free, b); continue; } /* keep draining the reader */
@@ -743,15 +771,16 @@ int mga_map_files_shard(const mg_idx_t *gi, int n_fn, const char **fn, const mg_
 			usleep(200);
 		}
 		w->fb = b, w->len = 0, w->seg = b->seg;
-		mga_stream_submit(S, b->n, b->qlens, (const char**)b->seqs, (const char**)b->names, 0, 1, 0, 0, b->pinned && b->base_pinned, (n_sub == 0 ? MGA_SB_FIRST : 0) | (b->last ? MGA_SB_LAST : 0), w->buf, w->cap, b);
+		mga_stream_submit(S, b->n, b->qlens, (const char**)b->seqs, (const char**)b->names, 0, cov == 0, 0, 0, b->pinned && b->base_pinned, (n_sub == 0 ? MGA_SB_FIRST : 0) | (b->last ? MGA_SB_LAST : 0), w->buf, w->cap, b);
 		w->buf = 0, w->cap = 0;
 		++n_sub;
 		chan_put(&c_sub, w);
 	}
 	chan_put(&c_sub, 0);
-	pthread_join(t_rd, 0); pthread_join(t_co, 0); pthread_join(t_wr, 0);
+	pthread_join(t_rd, 0); pthread_join(t_co, 0); if (!cov) pthread_join(t_wr, 0);
 	if (C.err) { mga_set_error("%s", C.errmsg); ret = -1; }
 	if (R.err || W.err) ret = -1;
+	mga_stream_set_cov(S, 0);
 	mga_idx_stream_release(S);
 	if (mem && ret == 0) { if (sink.mem == 0) sink.mem = (char*)calloc(1, 1), sink.mem_cap = 1; sink.mem[sink.mem_len] = 0; *mem = sink.mem, *mem_len = sink.mem_len; if (mem_cap) *mem_cap = sink.mem_cap; }
 	else { mga_host_unpin(sink.mem); free(sink.mem); }
@@ -771,12 +800,19 @@ int mg_map_files_fp(gfa_t *g, int n_fn, const char **fn, const mg_idxopt_t *ipt,
 	mg_idx_t *gi;
 	int ret;
 	double t_map = 0.0;
-	if (opt.flag & (MG_M_FRAG_MODE | MG_M_CAL_COV)) {
-		if (mg_verbose >= 1) fprintf(stderr, "[E::%s] --frag and --cov are outside the MI355X long-read path (single-segment reads, GAF output)\n", __func__);
+	if (opt.flag & MG_M_FRAG_MODE) {
+		if (mg_verbose >= 1) fprintf(stderr, "[E::%s] --frag is outside the MI355X long-read path (single-segment reads)\n", __func__);
+		mga_set_error("--frag (multi-segment fragments) is outside the MI355X long-read path");
 		return -1;
 	}
 	if ((gi = mg_index(g, ipt, n_threads, &opt)) == 0) return -1;
-	ret = mga_map_files_idx(gi, n_fn, fn, &opt, n_threads, out, 0, 0, &t_map);
+	if (opt.flag & MG_M_CAL_COV) { /* gmap.c:193-208: every file is mapped, nothing is printed, g's segments and links get their dc:f: -- printing the graph is the caller's (main.c:284-285) */
+		int64_t *seg_bases = MGA_CALLOC(int64_t, g->n_seg + 1), *link_cnt = MGA_CALLOC(int64_t, g->n_arc + 1);
+		double *cov_seg = MGA_CALLOC(double, g->n_seg + 1), *cov_link = MGA_CALLOC(double, g->n_arc + 1);
+		ret = mga_map_files_cov(gi, n_fn, fn, &opt, n_threads, 0, 1, seg_bases, link_cnt, 0, &t_map);
+		if (ret == 0) { mga_cov_finish(g, seg_bases, link_cnt, cov_seg, cov_link); mga_gfa_aux_update_cv(g, "dc", cov_seg, cov_link); }
+		free(seg_bases); free(link_cnt); free(cov_seg); free(cov_link);
+	} else ret = mga_map_files_idx(gi, n_fn, fn, &opt, n_threads, out, 0, 0, &t_map);
 	if (ret < 0) fprintf(stderr, "[E::%s] %s\n", __func__, mga_last_error());
 	if (mg_verbose >= 3) fprintf(stderr, "[M::%s] mapping phase %.3f s\n", __func__, t_map);
 	mg_idx_destroy(gi);

@@ -862,15 +862,16 @@ typedef struct { /* one pipeline context: HIP stream + grow-only device and pinn
 			mga_dbuf_t lcord; /* k_lchain's launch order: reads by anchor count, most first */
 			mga_dbuf_t rq_a, rq_f, rq_p, rq_v, rq_t, rq_pri, rq_ys, rq_cut, rq_ord, rq_stat, rq_cnt; /* forward pass of the RMQ chainer on the device (k_rmq.hip), one read at a time */
 			mga_dbuf_t g_line, g_qn, g_qoff, g_len, g_off, g_out; /* whole GAF lines on the device (k_gaf.hip): line records, read names, line lengths / offsets, the text */
+			mga_dbuf_t cv_chain, cv_vert; /* read coverage (k_cov.hip): chain records and walk vertices of the chunk */
 		};
-		mga_dbuf_t dall[73];
+		mga_dbuf_t dall[75];
 	};
 	union {
-		struct { mga_hbuf_t h_b, h_u, h_mini, h_tseq, h_prob, h_pool, h_seq, h_ncig, h_cigoff, h_item, h_chain, h_vert, h_txtres, h_txtpool, h_gchdr, h_gcpool, h_lcpool, h_apool, h_plrev, h_ploff, h_lcord, h_rq, h_rqs, h_plsrc, h_gline, h_gqn, h_gout; }; /* pinned staging */
-		mga_hbuf_t hall[27];
+		struct { mga_hbuf_t h_b, h_u, h_mini, h_tseq, h_prob, h_pool, h_seq, h_ncig, h_cigoff, h_item, h_chain, h_vert, h_txtres, h_txtpool, h_gchdr, h_gcpool, h_lcpool, h_apool, h_plrev, h_ploff, h_lcord, h_rq, h_rqs, h_plsrc, h_gline, h_gqn, h_gout, h_cvchain, h_cvvert; }; /* pinned staging */
+		mga_hbuf_t hall[29];
 	};
 } pipe_ctx_t;
-_Static_assert(sizeof(((pipe_ctx_t*)0)->dall) == 73 * sizeof(mga_dbuf_t) && sizeof(((pipe_ctx_t*)0)->hall) == 27 * sizeof(mga_hbuf_t), "pipe_ctx_t: buffer lists out of sync");
+_Static_assert(sizeof(((pipe_ctx_t*)0)->dall) == 75 * sizeof(mga_dbuf_t) && sizeof(((pipe_ctx_t*)0)->hall) == 29 * sizeof(mga_hbuf_t), "pipe_ctx_t: buffer lists out of sync");
 
 #define MGA_MAX_PIPE 8
 
@@ -1003,6 +1004,7 @@ typedef struct { /* one run of the stage sequence: a stack object of map_chunk()
 	pipe_ctx_t *P; const mg_idx_t *gi; const mg_mapopt_t *opt; int n, n_threads, seqs_pinned, lr_long;
 	const int *qlens; const char **seqs, **qnames; mg_gchains_t **gcs_out; mga_stats_t *st; kstring_t *gaf_part; const gaf_sink_t *sink;
 	const char *d_seq_res; const int64_t *q_off_res; /* the caller keeps the batch resident: the reads in HBM + absolute offsets */
+	mga_cov_job_t *cov; /* a coverage job (--cov): the chunk ends in chunk_cov() -- no GAF, no chains handed out */
 	chunk_knobs_t k;
 	/* mode flags */
 	int is_rmq, chunk_long; /* -x asm; -x lr, a chunk of ultra-long reads (batch_cut): the long-query path as well, first chaining pass on host threads (hchain.c: mga_lchain_dp_fwd) */
@@ -1355,7 +1357,7 @@ static int chunk_gchain_dev(chunk_t *c)
 	c->h_gchdr_p = (mga_gc_hdr_t*)P->h_gchdr.p;
 	CK(mga_d2h_s(sc, c->h_gchdr_p, P->gchdr.p, (size_t)n * sizeof(mga_gc_hdr_t)));
 	CK(mga_d2h_s(sc, P->h_gcpool.p, P->gcpool.p, (size_t)ctl[1] * rec)); CK(mga_d2h_s(sc, P->h_lcpool.p, P->lcpool.p, (size_t)ctl[2] * sizeof(mg_llchain_t)));
-	c->need_a = !c->dev_plan || (mg_dbg_flag & 0x8) || (opt->flag & MG_M_WRITE_LCHAIN); /* with the gap list made on the device, only the per-vertex lines (-S / --write-mz) read anchors on the host */
+	c->need_a = (!c->dev_plan && !c->cov) || (mg_dbg_flag & 0x8) || (opt->flag & MG_M_WRITE_LCHAIN); /* with the gap list made on the device, only the per-vertex lines (-S / --write-mz) read anchors on the host */
 	if (c->need_a) CK(mga_d2h_s(sc, P->h_apool.p, P->apool.p, (size_t)ctl[6] * 16));
 	CK(mga_ssync(sc)); /* (h_nu / h_nb / h_rflag arrived with the first sync) */
 	for (i = 0; i < n; ++i) /* the few reads whose rescue k_lchain left to the host tree: their chains, anchors and minimizer positions come down for the host path */
@@ -1666,6 +1668,61 @@ static int chunk_emit(chunk_t *c)
 	return 0;
 }
 
+/* ---- --cov: the chunk's chains end in the job's integer accumulators instead of GAF lines (cal_cov.c:8-53; cov_core.h, k_cov.hip) ----
+ * Every chain of every read is a 32-byte record (the fields of mg_gchain_t the count reads, MAPQ from the host's logf included) plus its walk, 4 bytes per vertex: both go
+ * up, k_cov filters and counts.  Whichever side chained the read, its walk reaches the device the same way, so the reads the device handed to the host threads
+ * (mga_gc_hdr_t::status != 0) need no path of their own.  The chains of -x asm and of chunks of ultra-long reads (walks of 10^5 vertices, a handful per chunk) are
+ * counted by this thread through the host instantiation, into the job's host-side accumulators.  Nothing comes down here: the accumulators do, once, when the job ends. */
+typedef struct { const mga_batch_t *b; const int64_t *c_off, *v_off; mga_cov_chain_t *chain; uint32_t *vert; } cov_export_t;
+static void cov_export_worker(void *data, int64_t i, int tid)
+{
+	cov_export_t *e = (cov_export_t*)data;
+	const mg_gchains_t *gcs = e->b->gcs[i];
+	int64_t ci = e->c_off[i], vi = e->v_off[i];
+	int32_t k, j;
+	(void)tid;
+	for (k = 0; gcs && k < gcs->n_gc; ++k) {
+		const mg_gchain_t *gc = &gcs->gc[k];
+		mga_cov_chain_t *r;
+		if (gc->cnt <= 0) continue;
+		r = &e->chain[ci++];
+		r->vert_beg = vi, r->vert_cnt = gc->cnt, r->ps = gc->ps, r->pe = gc->pe, r->plen = gc->plen, r->mapq = (int32_t)gc->mapq, r->blen = gc->blen;
+		for (j = 0; j < gc->cnt; ++j) e->vert[vi++] = gcs->lc[gc->off + j].v;
+	}
+}
+
+static int chunk_cov(chunk_t *c)
+{
+	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc; mga_batch_t *b = c->b; mga_cov_job_t *J = c->cov; const int n = c->n;
+	int64_t *off, n_chain = 0, n_vert = 0;
+	cov_export_t e;
+	int i, k, rc = -1;
+	if (c->is_rmq || c->chunk_long) {
+		for (i = 0; i < n; ++i) mga_cov_read_host(&J->G, b->gcs[i], J->min_mapq, J->min_blen, J->h_seg_bases, J->h_link_cnt, J->h_cnt);
+		return 0;
+	}
+	off = MGA_MALLOC(int64_t, 2 * ((size_t)n + 1));
+	for (i = 0; i < n; ++i) {
+		const mg_gchains_t *gcs = b->gcs[i];
+		off[i] = n_chain, off[n + 1 + i] = n_vert;
+		for (k = 0; gcs && k < gcs->n_gc; ++k) if (gcs->gc[k].cnt > 0) ++n_chain, n_vert += gcs->gc[k].cnt;
+	}
+	off[n] = n_chain, off[2 * n + 1] = n_vert;
+	if (n_chain > 0x7fffffffLL) { mga_set_error("too many graph chains in one chunk (%ld); lower MGA_CHUNK", (long)n_chain); goto done; }
+	if (n_chain == 0) { rc = 0; goto done; }
+	if (mga_hbuf_reserve(&P->h_cvchain, (size_t)n_chain * sizeof(mga_cov_chain_t) + 64) < 0 || mga_hbuf_reserve(&P->h_cvvert, (size_t)n_vert * 4 + 64) < 0 ||
+		mga_dbuf_reserve(&P->cv_chain, (size_t)n_chain * sizeof(mga_cov_chain_t) + 64) < 0 || mga_dbuf_reserve(&P->cv_vert, (size_t)n_vert * 4 + 64) < 0) goto done;
+	e.b = b, e.c_off = off, e.v_off = off + n + 1, e.chain = (mga_cov_chain_t*)P->h_cvchain.p, e.vert = (uint32_t*)P->h_cvvert.p;
+	mga_parallel_for(c->n_threads, n, cov_export_worker, &e);
+	if (mga_h2d_s(sc, P->cv_chain.p, P->h_cvchain.p, (size_t)n_chain * sizeof(mga_cov_chain_t)) < 0 || mga_h2d_s(sc, P->cv_vert.p, P->h_cvvert.p, (size_t)n_vert * 4) < 0 ||
+		mga_dev_cov(sc, &c->gi->B->dev, (int)n_chain, (const mga_cov_chain_t*)P->cv_chain.p, (const uint32_t*)P->cv_vert.p, n_vert, J->min_mapq, J->min_blen,
+					J->d_seg_bases, J->d_link_cnt, J->d_cnt) < 0 || mga_ssync(sc) < 0) goto done;
+	rc = 0;
+done:
+	free(off);
+	return rc;
+}
+
 static int chunk_stats(chunk_t *c)
 {
 	mga_stats_t *st = c->st; const int n = c->n;
@@ -1688,11 +1745,17 @@ static void chunk_release(chunk_t *c, int rc)
 }
 
 static int map_chunk(pipe_ctx_t *P, const mg_idx_t *gi, int n, const int *qlens, const char **seqs, const char **qnames, mg_gchains_t **gcs_out,
-					 const mg_mapopt_t *opt, int n_threads, const char *d_seq_res, const int64_t *q_off_res, int seqs_pinned, mga_stats_t *st, kstring_t *gaf_part, int lr_long, const gaf_sink_t *sink)
+					 const mg_mapopt_t *opt, int n_threads, const char *d_seq_res, const int64_t *q_off_res, int seqs_pinned, mga_stats_t *st, kstring_t *gaf_part, int lr_long, const gaf_sink_t *sink,
+					 mga_cov_job_t *cov)
 {
 	chunk_t c;
+	mg_mapopt_t opt_cov;
 	int rc = -1, i;
 	memset(&c, 0, sizeof c);
+	if (cov) { /* a coverage reads the chain records alone (cal_cov.c:17: gc->blen, not the CIGAR's): no gap is listed or aligned, with or without -c */
+		opt_cov = *opt, opt_cov.flag &= ~(uint64_t)MG_M_CIGAR, opt = &opt_cov;
+		gaf_part = 0, sink = 0, c.cov = cov;
+	}
 	c.P = P, c.gi = gi, c.opt = opt, c.n = n, c.qlens = qlens, c.seqs = seqs, c.qnames = qnames, c.gcs_out = gcs_out, c.n_threads = n_threads;
 	c.d_seq_res = d_seq_res, c.q_off_res = q_off_res, c.seqs_pinned = seqs_pinned, c.st = st, c.gaf_part = gaf_part, c.lr_long = lr_long, c.sink = sink;
 	chunk_knobs_read(&c.k);
@@ -1718,8 +1781,8 @@ static int map_chunk(pipe_ctx_t *P, const mg_idx_t *gi, int n, const int *qlens,
 	chunk_lap(&c, " wfa", &st->t_wfa);
 	if (chunk_finish(&c) < 0) goto done;
 	chunk_lap(&c, " hostpost", &st->t_host_post);
-	if (chunk_emit(&c) < 0) goto done;
-	if (gaf_part) chunk_lap(&c, " gaf", &st->t_gaf);
+	if (cov ? chunk_cov(&c) < 0 : chunk_emit(&c) < 0) goto done;
+	if (gaf_part || cov) chunk_lap(&c, cov ? " cov" : " gaf", &st->t_gaf);
 	rc = chunk_stats(&c);
 done:
 	chunk_release(&c, rc);
@@ -1769,6 +1832,7 @@ struct mga_stream_s {
 	pipe_ctx_t P[MGA_MAX_PIPE];
 	pthread_t thr[MGA_MAX_PIPE];
 	pthread_mutex_t api;           /* single-batch entry points on the index's stream: one call at a time */
+	mga_cov_job_t *cov;            /* the job in flight is a coverage job (set and cleared by its owner while nothing is in flight) */
 };
 
 typedef struct { kstring_t *part; int64_t *off; char *dst; } gcopy_t;
@@ -1869,7 +1933,7 @@ static void stream_run_chunk(mga_stream_t *S, pipe_ctx_t *P, sbatch_t *b, int c)
 	gaf_sink_t sink = { sink_try_reserve, sink_commit, &sink_ctx };
 	memset(&cst, 0, sizeof cst);
 	rc = b->err ? 0 : map_chunk(P, S->gi, en - st, b->qlens + st, b->seqs + st, b->qnames ? b->qnames + st : 0, b->gcs + st, &S->opt, b->n_threads,
-								b->d_seq, b->q_off ? b->q_off + st : 0, b->seqs_pinned, &cst, b->gaf_part ? b->gaf_part + (size_t)c * b->n_threads : 0, S->lr_long, b->gaf_part ? &sink : 0);
+								b->d_seq, b->q_off ? b->q_off + st : 0, b->seqs_pinned, &cst, b->gaf_part ? b->gaf_part + (size_t)c * b->n_threads : 0, S->lr_long, b->gaf_part ? &sink : 0, S->cov);
 	PIPE_LOG("map_chunk", c, tc);
 	if (rc == 0 && b->gaf_part && !b->err) { /* the chunk's GAF text was formatted inside map_chunk(); append it to the output in read order */
 		double t0 = mga_wtime();
@@ -2193,6 +2257,7 @@ mga_stream_t *mga_idx_stream_acquire(const mg_idx_t *gi, const mg_mapopt_t *opt,
 	S->n_submitted = 0; /* a new job: its first batch restarts the debug clocks */
 	return S;
 }
+void mga_stream_set_cov(mga_stream_t *S, mga_cov_job_t *J) { S->cov = J; }
 void mga_idx_stream_release(mga_stream_t *S) { pthread_mutex_unlock(&S->api); }
 
 void mga_idx_stream_close(mg_idx_t *gi) { if (gi && gi->B && gi->B->stream) { mga_stream_close((mga_stream_t*)gi->B->stream); gi->B->stream = 0; } }
@@ -2273,7 +2338,7 @@ void mg_map_frag(const mg_idx_t *gi, int n_segs, const int *qlens, const char **
 		memset(&cst, 0, sizeof cst);
 		if (g_dbg_pipe < 0) { g_dbg_pipe = env_int("MGA_DEBUG_PIPE", 0); g_gpu_wfa.avail = env_int("MGA_WFA_SLOTS", 2); g_gpu_front.avail = env_int("MGA_FRONT_SLOTS", 1); }
 		rc = mga_dev_init() < 0 || mga_dev_bind_thread() < 0 || (b->P.sc == 0 && (b->P.sc = mga_sctx_create()) == 0) ? -1 : 0;
-		if (rc == 0) rc = map_chunk(&b->P, gi, 1, qlens, seqs, &qname, gcs, opt, 1, 0, 0, 0, &cst, 0, (opt->flag & MG_M_RMQ) ? 0 : lr_long_bases(), 0);
+		if (rc == 0) rc = map_chunk(&b->P, gi, 1, qlens, seqs, &qname, gcs, opt, 1, 0, 0, 0, &cst, 0, (opt->flag & MG_M_RMQ) ? 0 : lr_long_bases(), 0, 0);
 		if (rc < 0) { fprintf(stderr, "[E::%s] %s\n", __func__, mga_last_error()); abort(); /* no CPU fallback */ }
 		pthread_mutex_lock(&g_stats_mtx); stats_merge(&gi->B->st, &cst); pthread_mutex_unlock(&g_stats_mtx);
 		return;

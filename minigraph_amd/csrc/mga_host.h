@@ -88,6 +88,20 @@ mga_stream_t *mga_idx_stream_acquire(const mg_idx_t *gi, const mg_mapopt_t *opt,
 void mga_idx_stream_release(mga_stream_t *S);
 void mga_idx_mf_free(mg_idx_t *gi);
 
+/* ---- a coverage job (cov.c): the integer accumulators of --cov, in HBM for the whole job (k_cov.hip adds to them from every chunk), and their host-side twins for
+ * the chains that host threads count (-x asm, chunks of ultra-long reads) ---- */
+typedef struct mga_cov_job_s {
+	int64_t n_seg, n_arc;
+	int32_t min_mapq, min_blen;
+	int64_t *d_seg_bases, *d_link_cnt, *d_cnt;
+	int64_t *h_seg_bases, *h_link_cnt, h_cnt[MGA_COV_N_CNT];
+	cov_graph_t G; int32_t *seg_len; /* the host's view of the graph for cov_core.h */
+} mga_cov_job_t;
+mga_cov_job_t *mga_cov_job_open(const mg_idx_t *gi, const mg_mapopt_t *opt);
+int mga_cov_job_close(mga_cov_job_t *J, int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st);
+void mga_cov_read_host(const cov_graph_t *G, const mg_gchains_t *gt, int32_t min_mapq, int32_t min_blen, int64_t *seg_bases, int64_t *link_cnt, int64_t *cnt);
+void mga_stream_set_cov(mga_stream_t *S, mga_cov_job_t *J); /* the chunks of the batches submitted from now on end in chunk_cov() (mapper.c); NULL: GAF / chains again */
+
 typedef struct { const char *cg, *ds; int32_t cg_len, ds_len, mlen, blen; } mga_chain_text_t; /* cg == NULL: format from the chain itself */
 #define MGA_KS_WINDOW 0xffffffffu /* kstring_t::m of a window into another buffer: never reallocated, never NUL-terminated (gaf.c) */
 void mga_gaf_window_limit(size_t bytes); /* the calling thread's next window holds this many bytes: a write past it aborts before it happens (gaf.c) */

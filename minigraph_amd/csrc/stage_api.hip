@@ -251,3 +251,29 @@ extern "C" int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, c
 	*u = ou, *u_off = uo, *b = ob, *b_off = bo;
 	return 0;
 }
+
+// mg_cov_map (cal_cov.c:8-53) for flat chain records through k_cov.hip against gi's graph replica; ADDS into seg_bases[n_seg] / link_cnt[n_arc] / *st
+extern "C" int mga_cov_batch(const mg_idx_t *gi, int n_chain, const mga_cov_chain_t *chain, int64_t n_vert, const uint32_t *vert, int32_t min_mapq, int32_t min_blen,
+							 int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st)
+{
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	const mga_didx_t *ix = &((const mg_idx_bucket_s_view*)gi->B)->dev;
+	const int64_t n_seg = gi->g->n_seg, n_arc = (int64_t)gi->g->n_arc;
+	for (int i = 0; i < n_chain; ++i) // the kernel does not follow such a record either; here the caller hears about it
+		if (chain[i].vert_cnt < 0 || chain[i].vert_beg < 0 || chain[i].vert_beg + chain[i].vert_cnt > n_vert) { mga_set_error("cov: chain %d points outside the %ld walk vertices", i, (long)n_vert); return -1; }
+	dptr d_chain, d_vert, d_seg, d_link, d_cnt;
+	if (!d_chain.alloc((size_t)(n_chain > 0 ? n_chain : 1) * sizeof(mga_cov_chain_t)) || !d_vert.alloc((size_t)n_vert * 4 + 16) || !d_seg.alloc((size_t)(n_seg + 1) * 8) ||
+		!d_link.alloc((size_t)(n_arc + 1) * 8) || !d_cnt.alloc(64)) return -1;
+	if (mga_dmemset_s(SC, d_seg.p, 0, (size_t)(n_seg + 1) * 8) < 0 || mga_dmemset_s(SC, d_link.p, 0, (size_t)(n_arc + 1) * 8) < 0 || mga_dmemset_s(SC, d_cnt.p, 0, 64) < 0) return -1;
+	if (n_chain > 0 && (mga_h2d(d_chain.p, chain, (size_t)n_chain * sizeof(mga_cov_chain_t)) < 0 || (n_vert > 0 && mga_h2d(d_vert.p, vert, (size_t)n_vert * 4) < 0))) return -1;
+	if (mga_dev_cov(SC, ix, n_chain, d_chain.as<mga_cov_chain_t>(), d_vert.as<uint32_t>(), n_vert, min_mapq, min_blen, d_seg.as<int64_t>(), d_link.as<int64_t>(), d_cnt.as<int64_t>()) < 0) return -1;
+	std::vector<int64_t> hs((size_t)n_seg + 1), hl((size_t)n_arc + 1);
+	int64_t cnt[8];
+	if (mga_ssync(SC) < 0 || mga_d2h(hs.data(), d_seg.p, (size_t)n_seg * 8) < 0 || mga_d2h(hl.data(), d_link.p, (size_t)n_arc * 8) < 0 || mga_d2h(cnt, d_cnt.p, 64) < 0) return -1;
+	for (int64_t i = 0; i < n_seg; ++i) seg_bases[i] += hs[i];
+	for (int64_t k = 0; k < n_arc; ++k) link_cnt[k] += hl[k];
+	if (st) st->chains_counted += cnt[MGA_COV_CHAINS], st->links_counted += cnt[MGA_COV_LINKS], st->links_skipped += cnt[MGA_COV_SKIPPED];
+	return 0;
+}

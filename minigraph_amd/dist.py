@@ -234,3 +234,19 @@ def map_sharded(mapper, dst=0, device="cpu", as_tensor=False):
     if as_tensor:
         return out
     return out.cpu().numpy().tobytes()
+
+
+def cov_sharded(graph, read_paths, n_threads=8, device="cpu", min_cov_mapq=None, min_cov_blen=None):
+    """read coverage (`--cov`) with the reads sharded over the ranks: every rank maps its shard into integer sums (mga_map_files_cov), then ONE all_reduce(SUM)
+    of the two int64 arrays (gloo on CPU tensors, RCCL on `device`).  Integer sums: every rank ends with exactly the single-process arrays.
+    Returns (seg_bases, link_cnt, cov_seg, cov_link) as numpy arrays."""
+    import numpy as np
+    import minigraph_amd as mga
+    rank, world = dist.get_rank(), dist.get_world_size()
+    sb, lc, _, _ = mga.map_cov_ints(graph, read_paths, n_threads, rank, world, min_cov_mapq, min_cov_blen)
+    t = torch.from_numpy(np.concatenate([sb, lc])).to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    t = t.cpu().numpy()
+    sb, lc = np.ascontiguousarray(t[:len(sb)]), np.ascontiguousarray(t[len(sb):])
+    cs, cl = mga.cov_finish(graph.g, sb, lc)
+    return sb, lc, cs, cl
