@@ -105,6 +105,10 @@ def load():
     L.mga_index_load_image.restype = C.c_void_p
     L.mga_seed_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, pp, pp, pp, pp, pp]
     L.mga_lchain_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(lchain_par_t), pp, pp, pp, pp]
+    L.mga_lchain_rescue_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(lchain_par_t), C.POINTER(rescue_par_t), C.c_void_p, pp, pp, pp, pp, C.c_void_p]
+    L.mga_lchain_rescue_batch.restype = C.c_int
+    L.mga_rmq_fwd_batch.argtypes = [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_float] + [C.c_void_p] * 4
+    L.mga_rmq_fwd_batch.restype = C.c_int
     L.mga_map_files_to_path.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(idxopt_t),
                                         C.POINTER(mapopt_t), C.c_int, C.c_char_p]
     L.mga_map_files_shard.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(mapopt_t), C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -265,8 +269,16 @@ class Graph:
         return [(aa[aoff[i]:aoff[i + 1]], int(rep[i]), mini[moff[i]:moff[i + 1]]) for i in range(n)]
 
 
-def lchain_batch(anchor_list, **kw):
-    """mg_lchain_dp for each read's x-sorted anchors -> list of (u, compacted anchors)"""
+class rescue_par_t(C.Structure):  # mga_rescue_par_t
+    _fields_ = [("enabled", C.c_int32), ("max_dist", C.c_int32), ("max_dist_inner", C.c_int32), ("bw", C.c_int32), ("max_skip", C.c_int32),
+                ("cap", C.c_int32), ("min_cnt", C.c_int32), ("min_sc", C.c_int32), ("chn_pen_gap", C.c_float), ("chn_pen_skip", C.c_float),
+                ("rescue_size", C.c_int32), ("rescue_ratio", C.c_float), ("frag_len", C.c_int32), ("frag_min_gap", C.c_int32)]
+
+
+def lchain_batch(anchor_list, rescue=None, qlens=None, **kw):
+    """mg_lchain_dp for each read's x-sorted anchors -> list of (u, compacted anchors).
+    rescue=dict(max_dist, max_dist_inner, bw, max_skip, cap, min_cnt, min_sc, pen_gap, pen_skip, rescue_size, rescue_ratio) with qlens (one query length per read):
+    the long-join rescue of the kernel is on (map-algo.c:407-417) -> list of (u, compacted anchors, flag), flag 0 first-pass chains / 1 rescued / 2 rescue due, handed back"""
     L = load()
     n = len(anchor_list)
     par = lchain_par_t(kw.get("max_dist_x", 5000), kw.get("max_dist_y", 5000), kw.get("bw", 500),
@@ -276,13 +288,45 @@ def lchain_batch(anchor_list, **kw):
     off[1:] = np.cumsum([len(a) for a in anchor_list])
     flat = np.ascontiguousarray(np.concatenate(anchor_list)) if n else np.zeros(0, dtype=m128)
     u, uo, b, bo = (C.c_void_p() for _ in range(4))
-    _check(L.mga_lchain_batch(n, flat.ctypes.data, off.ctypes.data, C.byref(par), C.byref(u), C.byref(uo),
-                              C.byref(b), C.byref(bo)), "mga_lchain_batch")
+    flag = None
+    if rescue is None:
+        _check(L.mga_lchain_batch(n, flat.ctypes.data, off.ctypes.data, C.byref(par), C.byref(u), C.byref(uo),
+                                  C.byref(b), C.byref(bo)), "mga_lchain_batch")
+    else:
+        if qlens is None or len(qlens) != n:
+            raise ValueError("lchain_batch: rescue needs one query length per read")
+        rs = rescue_par_t(1, rescue.get("max_dist", 5000), rescue.get("max_dist_inner", 1000), rescue.get("bw", 20000), rescue.get("max_skip", par.max_skip),
+                          rescue.get("cap", 100000), rescue.get("min_cnt", par.min_cnt), rescue.get("min_sc", par.min_sc),
+                          rescue.get("pen_gap", par.chn_pen_gap), rescue.get("pen_skip", par.chn_pen_skip),
+                          rescue.get("rescue_size", 1000), rescue.get("rescue_ratio", 0.1), 0, 0)
+        ql = np.ascontiguousarray(qlens, dtype=np.int32)
+        flag = np.full(n, -1, dtype=np.int32)
+        _check(L.mga_lchain_rescue_batch(n, flat.ctypes.data, off.ctypes.data, C.byref(par), C.byref(rs), ql.ctypes.data, C.byref(u), C.byref(uo),
+                                         C.byref(b), C.byref(bo), flag.ctypes.data), "mga_lchain_rescue_batch")
     uoff = _take(uo, n + 1, np.int64)
     boff = _take(bo, n + 1, np.int64)
     uu = _take(u, int(uoff[-1]), np.uint64)
     bb = _take(b, int(boff[-1]), m128)
+    if flag is not None:
+        return [(uu[uoff[i]:uoff[i + 1]], bb[boff[i]:boff[i + 1]], int(flag[i])) for i in range(n)]
     return [(uu[uoff[i]:uoff[i + 1]], bb[boff[i]:boff[i + 1]]) for i in range(n)]
+
+
+def rmq_fwd_batch(a, runs, order=None, max_dist=10000, max_dist_inner=1000, bw=2000, max_skip=25, cap=100000, pen_gap=0.8, pen_skip=0.05):
+    """forward pass of the RMQ chainer (k_rmq.hip) over the runs (beg, end, base) of one chunk-level x-sorted anchor array, one wavefront per run, in one launch;
+    order: run indices in launch order (None: the table's) -> (f, p, v, status): p counts from the run's base (-1: none), status 0 / 1 (tie) / 2 (inner window
+    beyond the kernel's sort) per run, 4 for a run the kernel never took"""
+    L = load()
+    a = np.ascontiguousarray(a, dtype=m128)
+    runs = np.ascontiguousarray(np.asarray(runs, dtype=np.int64).reshape(-1, 3))
+    n, n_runs = len(a), len(runs)
+    f, p, v = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    status = np.zeros(n_runs, dtype=np.int32)
+    od = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    _check(L.mga_rmq_fwd_batch(n, a.ctypes.data, n_runs, runs.ctypes.data, n_runs if od is None else len(od), None if od is None else od.ctypes.data,
+                               max_dist, max_dist_inner, bw, max_skip, cap, pen_gap, pen_skip, f.ctypes.data, p.ctypes.data, v.ctypes.data, status.ctypes.data),
+           "mga_rmq_fwd_batch")
+    return f, p, v, status
 
 
 def gaf_div_batch(div):

@@ -295,6 +295,13 @@ typedef struct { int64_t beg, end, base; } mga_rq_run_t;
 int mga_dev_rmq_fwd(mga_sctx_t *sc, int64_t n_total, const mg128_t *d_a, int n_order, const void *d_runs, const int32_t *d_order, int max_dist, int max_dist_inner, int bw,
 					int max_skip, int cap, float pen_gap, float pen_skip, int32_t *d_f, int64_t *d_p, int32_t *d_v, int32_t *d_t, double *d_pri, int32_t *d_ys,
 					int32_t *d_status, int *d_counter);
+/* stage tests (stage_api.hip; host pointers in and out).  mga_rmq_fwd_batch: the launch above over n_runs triples { beg, end, base } of the x-sorted chunk array a[n_total];
+ * order: n_order run indices, or NULL for the table's order (n_order is then n_runs).  Out: f, p, v per anchor (zero where no run wrote), status per run, 4 where the kernel
+ * never came.  mga_lchain_rescue_batch: mga_lchain_batch with the long-join rescue switched on: qlen[n] query lengths in, flag[n] (0 / 1 / 2, see mga_dev_lchain) out. */
+int mga_rmq_fwd_batch(int64_t n_total, const mg128_t *a, int n_runs, const int64_t *runs, int n_order, const int32_t *order, int max_dist, int max_dist_inner, int bw,
+					  int max_skip, int cap, float pen_gap, float pen_skip, int32_t *f, int64_t *p, int32_t *v, int32_t *status);
+int mga_lchain_rescue_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par, const mga_rescue_par_t *resc, const int32_t *qlen,
+							uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off, int32_t *flag);
 
 /* targets of HOST-listed gaps spliced on the device: problem j's target = the walk d_vert[src[j].lc0 .. + n_lc] from base x0 + 1 to base x1, written at d_tseq + prob[j].t_off */
 int mga_dev_plan_target_verts(mga_sctx_t *sc, const mga_didx_t *ix, int64_t n_prob, const mga_wfa_prob_t *d_prob, const mga_plan_src_t *d_src, const uint32_t *d_vert, char *d_tseq);

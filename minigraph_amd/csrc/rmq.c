@@ -292,6 +292,7 @@ static inline int32_t score_simple(const mg128_t *ai, const mg128_t *aj, float p
  * formulation (a device arg-min over the window) can reproduce?  Brute force over the window per query; counters per process. */
 static int g_tie_on = -1;
 static int64_t g_tie[8]; /* runs, runs with a tie, anchors, anchors of runs with a tie, queries with an answer, tied queries, sum of window sizes, longest run */
+void mga_rq_tie_stats_enable(int on) { g_tie_on = on ? 1 : 0; } /* at run time (tests): the environment is read once per process, and only while this was never called */
 void mga_rq_tie_stats(int64_t *out, int reset) { int k; for (k = 0; k < 8; ++k) { out[k] = __atomic_load_n(&g_tie[k], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_tie[k], 0, __ATOMIC_RELAXED); } }
 
 /* Forward pass of mg_lchain_rmq (lchain.c:275-353) over anchors [beg,end) of the x-sorted array a[]: fills f, p, v and the skip

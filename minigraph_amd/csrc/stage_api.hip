@@ -217,8 +217,9 @@ extern "C" int mga_sort128x_batch(int n, mg128_t *a, const int64_t *a_off)
 	return 0;
 }
 
-extern "C" int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par,
-								uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off)
+// resc / qlen / flag all given: the long-join rescue of k_lchain is on (mga_lchain_rescue_batch); all 0: the first pass alone (mga_lchain_batch)
+static int lchain_batch_impl(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par, const mga_rescue_par_t *resc, const int32_t *qlen,
+							 uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off, int32_t *flag)
 {
 	*u = 0, *u_off = 0, *b = 0, *b_off = 0;
 	if (mga_dev_init() < 0) return -1;
@@ -226,18 +227,25 @@ extern "C" int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, c
 	if (SC == 0) return -1;
 	if (n <= 0) { *u_off = (int64_t*)calloc(1, 8); *b_off = (int64_t*)calloc(1, 8); return 0; }
 	const int64_t tot = a_off[n];
-	dptr d_a, d_aoff, d_u, d_b, d_nu, d_nb, d_ws;
+	dptr d_a, d_aoff, d_u, d_b, d_nu, d_nb, d_ws, d_qoff, d_flag;
 	const size_t wsb = mga_dev_lchain_ws_bytes(tot);
 	if (!d_a.alloc((size_t)tot * 16 + 16) || !d_aoff.alloc((n + 1) * 8) || !d_u.alloc((size_t)tot * 8 + 8) || !d_b.alloc((size_t)tot * 16 + 16) ||
 		!d_nu.alloc(n * 4) || !d_nb.alloc(n * 4) || !d_ws.alloc(wsb)) return -1;
 	if (mga_h2d(d_a.p, a, (size_t)tot * 16) < 0 || mga_h2d(d_aoff.p, a_off, (n + 1) * 8) < 0) return -1;
-	if (mga_dev_lchain(SC, n, d_a.as<mg128_t>(), d_aoff.as<int64_t>(), par, 0, 0, d_u.as<uint64_t>(), d_b.as<mg128_t>(), d_nu.as<int32_t>(), d_nb.as<int32_t>(), 0,
-					   d_ws.p, wsb, tot) < 0) return -1;
+	if (resc) { // the pipeline's d_q_off: the reads' lengths as a prefix array
+		std::vector<int64_t> q_off((size_t)n + 1);
+		q_off[0] = 0;
+		for (int i = 0; i < n; ++i) q_off[i + 1] = q_off[i] + qlen[i];
+		if (!d_qoff.alloc((n + 1) * 8) || !d_flag.alloc(n * 4) || mga_h2d(d_qoff.p, q_off.data(), (n + 1) * 8) < 0) return -1;
+	}
+	if (mga_dev_lchain(SC, n, d_a.as<mg128_t>(), d_aoff.as<int64_t>(), par, resc, d_qoff.as<int64_t>(), d_u.as<uint64_t>(), d_b.as<mg128_t>(), d_nu.as<int32_t>(), d_nb.as<int32_t>(),
+					   d_flag.as<int32_t>(), d_ws.p, wsb, tot) < 0) return -1;
 	std::vector<int32_t> nu(n), nb(n);
 	std::vector<uint64_t> hu((size_t)tot + 1);
 	std::vector<mg128_t> hb((size_t)tot + 1);
 	if (mga_ssync(SC) < 0 || mga_d2h(nu.data(), d_nu.p, n * 4) < 0 || mga_d2h(nb.data(), d_nb.p, n * 4) < 0 ||
 		mga_d2h(hu.data(), d_u.p, (size_t)tot * 8) < 0 || mga_d2h(hb.data(), d_b.p, (size_t)tot * 16) < 0) return -1;
+	if (resc && mga_d2h(flag, d_flag.p, n * 4) < 0) return -1;
 	int64_t *uo = (int64_t*)malloc((n + 1) * 8), *bo = (int64_t*)malloc((n + 1) * 8);
 	int64_t tu = 0, tb = 0;
 	for (int i = 0; i < n; ++i) { uo[i] = tu, bo[i] = tb; tu += nu[i], tb += nb[i]; }
@@ -249,6 +257,54 @@ extern "C" int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, c
 		memcpy(ob + bo[i], hb.data() + a_off[i], (size_t)nb[i] * 16);
 	}
 	*u = ou, *u_off = uo, *b = ob, *b_off = bo;
+	return 0;
+}
+
+extern "C" int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par,
+								uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off)
+{
+	return lchain_batch_impl(n, a, a_off, par, 0, 0, u, u_off, b, b_off, 0);
+}
+
+// stage test of the long-join rescue inside k_lchain (lc_dp_rmq_lds / lc_dp_rmq and what lc_read_finish does when they hand a read back): tests/test_gpu_rmq.py
+extern "C" int mga_lchain_rescue_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par, const mga_rescue_par_t *resc, const int32_t *qlen,
+									   uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off, int32_t *flag)
+{
+	if (resc == 0 || qlen == 0 || flag == 0) { mga_set_error("lchain_rescue_batch: rescue parameters, query lengths and the flag array are required"); return -1; }
+	for (int i = 0; i < n; ++i) if (qlen[i] < 0) { mga_set_error("lchain_rescue_batch: read %d has a negative length", i); return -1; }
+	return lchain_batch_impl(n, a, a_off, par, resc, qlen, u, u_off, b, b_off, flag);
+}
+
+// stage test of the RMQ chainer's forward pass (k_rmq.hip): what rq_dev_fwd_hook (mapper.c) allocates and uploads for a chunk, one launch on the default stage stream, f / p / v
+// and the runs' status back.  A status the kernel never wrote stays 4, as in the pipeline.  tests/test_gpu_rmq.py
+extern "C" int mga_rmq_fwd_batch(int64_t n_total, const mg128_t *a, int n_runs, const int64_t *runs, int n_order, const int32_t *order, int max_dist, int max_dist_inner, int bw,
+								 int max_skip, int cap, float pen_gap, float pen_skip, int32_t *f, int64_t *p, int32_t *v, int32_t *status)
+{
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	if (n_total < 0 || n_runs < 0 || n_total >= 0x7fffffffLL) { mga_set_error("rmq_fwd_batch: bad sizes"); return -1; }
+	if (order == 0) n_order = n_runs;
+	for (int r = 0; r < n_runs; ++r) { // the kernel trusts its table
+		const int64_t beg = runs[3 * r], end = runs[3 * r + 1], base = runs[3 * r + 2];
+		if (!(0 <= base && base <= beg && beg <= end && end <= n_total)) { mga_set_error("rmq_fwd_batch: run %d lies outside the %ld anchors", r, (long)n_total); return -1; }
+	}
+	if (n_order < 0 || n_order > n_runs) { mga_set_error("rmq_fwd_batch: more work items than runs"); return -1; }
+	for (int k = 0; order && k < n_order; ++k)
+		if (order[k] < 0 || order[k] >= n_runs) { mga_set_error("rmq_fwd_batch: order[%d] names no run", k); return -1; }
+	for (int r = 0; r < n_runs; ++r) status[r] = 4;
+	if (n_total > 0) { memset(f, 0, (size_t)n_total * 4); memset(p, 0, (size_t)n_total * 8); memset(v, 0, (size_t)n_total * 4); }
+	if (n_total == 0 || n_order == 0) return 0;
+	const size_t n = (size_t)n_total;
+	dptr d_a, d_f, d_p, d_v, d_t, d_pri, d_ys, d_runs, d_ord, d_stat, d_cnt;
+	if (!d_a.alloc(n * 16 + 64) || !d_f.alloc(n * 4 + 64) || !d_p.alloc(n * 8 + 64) || !d_v.alloc(n * 4 + 64) || !d_t.alloc(n * 4 + 64) || !d_pri.alloc(n * 8 + 64) ||
+		!d_ys.alloc(n * 4 + 64) || !d_runs.alloc((size_t)n_runs * 24 + 64) || !d_ord.alloc((size_t)n_runs * 4 + 64) || !d_stat.alloc((size_t)n_runs * 4 + 64) || !d_cnt.alloc(64)) return -1;
+	if (mga_h2d(d_a.p, a, n * 16) < 0 || mga_h2d(d_runs.p, runs, (size_t)n_runs * 24) < 0 || mga_h2d(d_stat.p, status, (size_t)n_runs * 4) < 0) return -1;
+	if (order && mga_h2d(d_ord.p, order, (size_t)n_order * 4) < 0) return -1;
+	if (mga_dmemset_s(SC, d_t.p, 0, n * 4) < 0 || mga_dmemset_s(SC, d_f.p, 0, n * 4) < 0 || mga_dmemset_s(SC, d_p.p, 0, n * 8) < 0 || mga_dmemset_s(SC, d_v.p, 0, n * 4) < 0) return -1;
+	if (mga_dev_rmq_fwd(SC, n_total, d_a.as<mg128_t>(), n_order, d_runs.p, order ? d_ord.as<int32_t>() : 0, max_dist, max_dist_inner, bw, max_skip, cap, pen_gap, pen_skip,
+						d_f.as<int32_t>(), d_p.as<int64_t>(), d_v.as<int32_t>(), d_t.as<int32_t>(), d_pri.as<double>(), d_ys.as<int32_t>(), d_stat.as<int32_t>(), (int*)d_cnt.p) < 0) return -1;
+	if (mga_ssync(SC) < 0 || mga_d2h(f, d_f.p, n * 4) < 0 || mga_d2h(p, d_p.p, n * 8) < 0 || mga_d2h(v, d_v.p, n * 4) < 0 || mga_d2h(status, d_stat.p, (size_t)n_runs * 4) < 0) return -1;
 	return 0;
 }
 
