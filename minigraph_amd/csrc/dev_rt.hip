@@ -77,7 +77,7 @@ extern "C" mga_sctx_t *mga_sctx_create(void)
 	hipStream_t st;
 	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { free(sc); mga_set_error("hipStreamCreate failed"); return 0; }
 	sc->stream = (void*)st;
-	for (int i = 0; i < MGA_WFA_MAX_TIER; ++i) {
+	for (int i = 0; i < MGA_WFA_MAX_TIER; ++i) { // a sweep of the WFA ladder uses two of these streams and four of the events; all 16 + 16 stay, since the order of creation decides which hardware queue a stream lands on
 		hipStream_t t; hipEvent_t e;
 		if (hipStreamCreateWithFlags(&t, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { mga_set_error("hipStreamCreate failed"); return 0; }
 		sc->tier_stream[i] = (void*)t, sc->ev_done[i] = (void*)e;
@@ -99,7 +99,7 @@ extern "C" void mga_sctx_destroy(mga_sctx_t *sc)
 	if (sc == 0) return;
 	(void)hipStreamSynchronize((hipStream_t)sc->stream);
 	for (int i = 0; i < 10; ++i) mga_dbuf_free(&sc->wfa_ws[i]);
-	for (int i = 0; i < 8; ++i) mga_dbuf_free(&sc->wfa_tbuf[i]);
+	for (int i = 0; i < 2; ++i) mga_dbuf_free(&sc->wfa_tbuf[i]);
 	mga_dbuf_free(&sc->wfa_cnt);
 	mga_dbuf_free(&sc->scan_tmp); mga_dbuf_free(&sc->txt_cnt); mga_dbuf_free(&sc->txt_off); mga_dbuf_free(&sc->txt_vwb); mga_dbuf_free(&sc->txt_el);
 	mga_dbuf_free(&sc->wfa_list[0]); mga_dbuf_free(&sc->wfa_list[1]); mga_dbuf_free(&sc->wfa_key); mga_dbuf_free(&sc->wfa_ctl); mga_dbuf_free(&sc->wfa_fb);
@@ -111,29 +111,6 @@ extern "C" void mga_sctx_destroy(mga_sctx_t *sc)
 	if (sc->stage) { mga_hfree_pinned(((stage_t*)sc->stage)->buf); free(sc->stage); }
 	(void)hipStreamDestroy((hipStream_t)sc->stream);
 	free(sc);
-}
-
-// The tiers of one chunk run one after another on the context's stream: [measured] 1.95 vs 1.85 Gbp/s against running them
-// concurrently on their own streams -- co-resident tiers halve each other's occupancy, while the tails of the wide tiers are
-// filled by the kernels of the OTHER chunks in the pipeline anyway.  MGA_WFA_CONCURRENT=1 brings the per-tier streams back.
-static int wfa_serial(void) { return 1; } // (round 3: a sweep of the ladder is one chain of launches -- a rung reads what the rungs before it appended)
-extern "C" int mga_wfa_tiers_serial(void) { return wfa_serial(); }
-extern "C" void *mga_wfa_stream(mga_sctx_t *sc, int slot) { return wfa_serial() ? sc->stream : sc->tier_stream[slot % MGA_WFA_MAX_TIER]; }
-
-extern "C" int mga_wfa_fork(mga_sctx_t *sc)
-{
-	MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_ready, (hipStream_t)sc->stream));
-	for (int i = 0; i < MGA_WFA_MAX_TIER; ++i) MGA_HIP_CHECK(hipStreamWaitEvent((hipStream_t)sc->tier_stream[i], (hipEvent_t)sc->ev_ready, 0));
-	return 0;
-}
-
-extern "C" int mga_wfa_join(mga_sctx_t *sc)
-{
-	for (int i = 0; i < MGA_WFA_MAX_TIER; ++i) {
-		MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_done[i], (hipStream_t)sc->tier_stream[i]));
-		MGA_HIP_CHECK(hipStreamWaitEvent((hipStream_t)sc->stream, (hipEvent_t)sc->ev_done[i], 0));
-	}
-	return 0;
 }
 
 extern "C" mga_sctx_t *mga_sctx_default(void)

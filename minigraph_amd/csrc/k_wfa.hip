@@ -316,9 +316,9 @@ static const wfa_cfg_t g_tier[3] = {
 static const int g_tier_waves[3] = { 256, 16, 1 };
 
 
-extern "C" int mga_dev_wfa(mga_sctx_t *sc, const int *d_n, int n, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-						   mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt)
+extern "C" int mga_dev_wfa(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier)
 {
+	const int n = ln->cap, first = ln->first;
 	if (n <= 0) return 0;
 	if (tier < 0 || tier > 1) { mga_set_error("wfa: bad tier %d", tier); return -1; }
 	if (sc->wfa_uncapped) tier = tier == 1 ? 2 : tier; // ladder of the fallback's sub-problems: same first HBM tier, then the unbounded one
@@ -336,12 +336,12 @@ extern "C" int mga_dev_wfa(mga_sctx_t *sc, const int *d_n, int n, int first, int
 	int waves = g_tier_waves[tier];
 	if (waves > n - first) waves = n - first;
 	if (mga_dbuf_reserve(&sc->wfa_ws[7 + tier], (size_t)cfg.ws_stride * waves) < 0) return -1;
-	hipStream_t st = (hipStream_t)(stream ? stream : sc->stream);
-	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * slot);
+	hipStream_t st = (hipStream_t)(ln->stream ? ln->stream : sc->stream);
+	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * ln->slot);
 	const int kid = MGA_K_WFA0 + 7 + (tier > 1 ? 1 : tier); // the unbounded tier is accounted with the widest regular one
 	mga_prof_begin(st, kid);
-	hipLaunchKernelGGL(k_wfa, dim3(waves), dim3(64), 0, st, d_n, n, first, d_list, d_prob, d_tseq, d_qseq, d_res, d_pool, (long long)pool_cap,
-					   d_pool_used, (char*)sc->wfa_ws[7 + tier].p, d_counter, rt, cfg);
+	hipLaunchKernelGGL(k_wfa, dim3(waves), dim3(64), 0, st, ln->d_n, n, first, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, job->d_pool, (long long)job->pool_cap,
+					   job->d_pool_used, (char*)sc->wfa_ws[7 + tier].p, d_counter, ln->rt, cfg);
 	mga_prof_end(st, kid);
 	MGA_HIP_CHECK(hipGetLastError());
 	return 0;

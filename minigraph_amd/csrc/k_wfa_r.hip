@@ -415,9 +415,9 @@ static const wfr_tier_t g_rtier[7] = {
 	{   64,  16384,  12 << 20 },  // 16 waves x 2 slots: 2048 (a handful of problems per 10^5 reads; keeps them off the slow HBM kernel)
 };
 
-extern "C" int mga_dev_wfa_reg(mga_sctx_t *sc, const int *d_n, int n, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-							   mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt)
+extern "C" int mga_dev_wfa_reg(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier)
 {
+	const int n = ln->cap, first = ln->first;
 	if (n <= 0) return 0;
 	if (tier < 0 || tier > 6) { mga_set_error("wfa_reg: bad tier %d", tier); return -1; }
 	const wfr_tier_t &T = g_rtier[tier];
@@ -426,10 +426,10 @@ extern "C" int mga_dev_wfa_reg(mga_sctx_t *sc, const int *d_n, int n, int first,
 	int wgs = T.n_wg < n - first ? T.n_wg : n - first; // (n: the list's capacity; the kernel sizes its queue chunks by the list's real length)
 	if (wgs < 1) wgs = 1;
 	if (mga_dbuf_reserve(&sc->wfa_ws[tier], (size_t)cfg.ws_stride * T.n_wg) < 0) return -1;
-	hipStream_t st = (hipStream_t)(stream ? stream : sc->stream);
-	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * slot);
+	hipStream_t st = (hipStream_t)(ln->stream ? ln->stream : sc->stream);
+	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * ln->slot);
 	mga_prof_begin(st, MGA_K_WFA0 + tier);
-#define LAUNCH(NW, JJ, SEQ, SM, TBL, HBM) hipLaunchKernelGGL((k_wfa_r<NW, JJ, SEQ, SM, TBL, HBM>), dim3(wgs), dim3(64 * NW), 0, st, d_n, n, first, d_list, d_prob, d_tseq, d_qseq, d_res, d_pool, (long long)pool_cap, d_pool_used, (char*)sc->wfa_ws[tier].p, d_counter, rt, cfg)
+#define LAUNCH(NW, JJ, SEQ, SM, TBL, HBM) hipLaunchKernelGGL((k_wfa_r<NW, JJ, SEQ, SM, TBL, HBM>), dim3(wgs), dim3(64 * NW), 0, st, ln->d_n, n, first, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, job->d_pool, (long long)job->pool_cap, job->d_pool_used, (char*)sc->wfa_ws[tier].p, d_counter, ln->rt, cfg)
 	if (tier == 0) LAUNCH(1, 1, 128, 64, 2048, false); // (g_rtier[0].tbcap == 0: traceback in LDS only)
 	else if (tier == 1) LAUNCH(1, 2, 256, 128, 4096, true);
 	else if (tier == 2) LAUNCH(1, 3, 256, 192, 6144, true); // [measured] 60 ns per problem against 87 ns in the two-wave 256-diagonal tier; the centre slot alone holds the first 32 scores

@@ -2,15 +2,15 @@
 //
 // Every problem starts in the cheapest tier its length suggests; a problem that outgrows its tier is appended by
 // the kernel itself to the next tier's work list (mga_wfa_retry_t).  The host only reads a handful of counters
-// per pass -- it never walks the (millions of) problems.
-//   pass 0:  counting sort of the problem ids by (tier, decreasing length): k_wfa_bin_count -> k_wfa_bin_scan ->
-//            k_wfa_bin_scatter.  Longest-first inside a tier starts the slow problems early instead of leaving
-//            them as the tail of the launch.
-//   pass p:  the retry lists written during pass p-1, one tier up (double-buffered work lists).
-// All tiers of a pass run concurrently on their own streams (mga_wfa_fork / mga_wfa_join).
+// per sweep -- it never walks the (millions of) problems.
+//   binning: counting sort of the problem ids by (rung, decreasing length): k_wfa_bin_count -> k_wfa_bin_scan -> k_wfa_bin_scatter.
+//            Longest-first inside a rung starts the slow problems early instead of leaving them as the tail of the launch.
+//   a sweep: every rung ONCE, in ascending order, on the context's stream; a rung's launch reads its list's length on the device,
+//            so it also takes what the rungs below it appended (wfs_sweep).  Two side streams: the own problems of the register /
+//            HBM rungs, and (MGA_WFA_TB_SIDE=1) the windowed rungs' walks.
+//   after:   sweeps over what a full list left open, the low-memory rung, the chained fallback (mga_dev_wfa_solve).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-#include <time.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
@@ -56,14 +56,6 @@ __host__ __device__ __forceinline__ int wfs_first_rung(int32_t tl, int32_t ql, c
 	const int32_t m = tl > ql ? tl : ql;
 	for (int k = 0; k < T.n - 1; ++k) if (m <= T.t[k]) return k;
 	return T.n - 1;
-}
-
-extern "C" int mga_wfa_first_tier(int32_t tl, int32_t ql) // (round-2 stage API: first register tier by length)
-{
-	const wfs_ladder_t *L = &g_ladder_old;
-	const int32_t m = tl > ql ? tl : ql;
-	for (int k = 0; k < L->n; ++k) if (m <= L->r[k].maxlen) return k;
-	return L->n - 1;
 }
 
 __global__ void __launch_bounds__(1024) k_wfa_bin_count(int n, const int32_t *__restrict__ ids /* NULL: problems 0..n-1 */, const mga_wfa_prob_t *__restrict__ prob, int32_t *__restrict__ key, int *__restrict__ hist, wfs_thr_t T)
@@ -211,30 +203,28 @@ __global__ void __launch_bounds__(256) k_wfa_gather(int n, const mga_wfa_res_t *
 	}
 }
 
-extern "C" int mga_dev_wfa_gather(mga_sctx_t *sc, int n, const mga_wfa_res_t *d_res, const uint32_t *d_pool, int32_t *d_ncig, int64_t *d_off, uint32_t *d_ord,
-								  int64_t ord_cap, int64_t *h_total)
+extern "C" int mga_dev_wfa_gather(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, int32_t *d_ncig, int64_t *d_off, uint32_t *d_ord, int64_t ord_cap, int64_t *h_total)
 {
 	*h_total = 0;
 	if (n <= 0) return 0;
 	hipStream_t st = (hipStream_t)sc->stream;
 	long long tot = 0;
-	hipLaunchKernelGGL(k_wfa_ncig, dim3((n + 255) / 256), dim3(256), 0, st, n, d_res, d_ncig);
+	hipLaunchKernelGGL(k_wfa_ncig, dim3((n + 255) / 256), dim3(256), 0, st, n, (const mga_wfa_res_t*)job->d_res, d_ncig);
 	MGA_HIP_CHECK(hipGetLastError());
 	if (mga_dev_scan_i32_to_i64(sc, d_ncig, n, d_off) < 0) return -1;
 	if (mga_d2h_s(sc, &tot, d_off + n, 8) < 0 || mga_ssync(sc) < 0) return -1;
 	if (tot > ord_cap) { mga_set_error("WFA gather: %lld operators exceed the buffer of %lld", tot, (long long)ord_cap); return -1; }
-	hipLaunchKernelGGL(k_wfa_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, d_res, (const int64_t*)d_off, d_pool, d_ord);
+	hipLaunchKernelGGL(k_wfa_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, (const mga_wfa_res_t*)job->d_res, (const int64_t*)d_off, (const uint32_t*)job->d_pool, d_ord);
 	MGA_HIP_CHECK(hipGetLastError());
 	*h_total = (int64_t)tot;
 	return 0;
 }
 
-extern "C" int mga_dev_wfa_tier(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-								mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt)
+extern "C" int mga_dev_wfa_tier(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier)
 {
-	if (cap - first <= 0) return 0;
-	if (tier < 7) return mga_dev_wfa_reg(sc, d_n, cap, first, slot, stream, d_list, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, tier, rt);
-	return mga_dev_wfa(sc, d_n, cap, first, slot, stream, d_list, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, tier - 7, rt); /* HBM tiers with 4096 / 32768 diagonals */
+	if (ln->cap - ln->first <= 0) return 0;
+	if (tier < 7) return mga_dev_wfa_reg(sc, job, ln, tier);
+	return mga_dev_wfa(sc, job, ln, tier - 7); /* HBM tiers with 4096 / 32768 diagonals */
 }
 
 // problems a sweep left undecided (their rung's list was full): collected for the next sweep
@@ -255,6 +245,34 @@ __global__ void __launch_bounds__(256) k_wfa_mark_pending(int n, mga_wfa_res_t *
 	if (i < n) res[i].status = MGA_WFA_PENDING;
 }
 
+// The device control block of a ladder call (sc->wfa_ctl): 32-bit words; the kernels get raw int pointers into it, the host derives them from this layout.
+struct wfs_ctl_t {
+	int hist[WFS_NBIN];               // k_wfa_bin_count's histogram, then the cursors of k_wfa_bin_scatter
+	int tier_off[16];                 // first list slot of every rung, [MGA_WFA_N_SLOT] = the number of problems (k_wfa_bin_scan)
+	int rc[32];                       // rc[t]: length of rung t's list (own problems, then arrivals); rc[WFS_RC_OVER]: problems that fell off the last rung.  (A sweep reads the first 16 back.)
+	int err, fb;                      // problems that failed; problems that hit the cell cap (listed in sc->wfa_fb for the chained fallback).  A sweep's memset stops before `err`: these are kept across sweeps
+	int cells[2];                     // 64-bit sum of k_wfa_sum_cells at the end; until then two free words: the counter of wfs_collect_open()
+};
+enum { WFS_RC_OVER = 15 };
+static_assert(offsetof(wfs_ctl_t, tier_off) == 4 * WFS_NBIN && offsetof(wfs_ctl_t, rc) == 4 * (WFS_NBIN + 16) && offsetof(wfs_ctl_t, err) == 4 * (WFS_NBIN + 48) &&
+			  offsetof(wfs_ctl_t, fb) == 4 * (WFS_NBIN + 49) && offsetof(wfs_ctl_t, cells) == 4 * (WFS_NBIN + 50) && sizeof(wfs_ctl_t) == 4 * (WFS_NBIN + 52) &&
+			  offsetof(wfs_ctl_t, cells) % 8 == 0 && MGA_WFA_N_SLOT < WFS_RC_OVER, "layout of the WFA control block: the kernels' pointers and the memset spans must not move");
+// The work-queue counter lines of a sweep's launches (sc->wfa_cnt: 64 lines of 64 bytes, zeroed per sweep): base + the tier's index within its kind
+enum { WFS_CNT_OWN = 0 /* register / HBM rungs, own problems (tiers 0-8) */, WFS_CNT_WIN = 9 /* windowed rungs (0-5) */, WFS_CNT_ARR = 32 /* register / HBM rungs, arrivals */ };
+
+// Lists the problems of 0 .. n-1 that are still open in sc->wfa_list[1] (in completion order) and returns their number (< 0: error).  d_cnt: two free words of the control block, left zeroed.
+static int wfs_collect_open(mga_sctx_t *sc, int n, const mga_wfa_res_t *d_res, int *d_cnt)
+{
+	hipStream_t st = (hipStream_t)sc->stream;
+	int k = 0;
+	if (mga_dbuf_reserve(&sc->wfa_list[1], (size_t)n * 4 + 64) < 0) return -1;
+	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
+	hipLaunchKernelGGL(k_wfa_collect_open, dim3((n + 255) / 256), dim3(256), 0, st, n, d_res, (int32_t*)sc->wfa_list[1].p, d_cnt);
+	MGA_HIP_CHECK(hipGetLastError());
+	if (mga_d2h_s(sc, &k, d_cnt, 4) < 0 || mga_ssync(sc) < 0) return -1;
+	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
+	return k;
+}
 
 // ---- chained fallback ---------------------------------------------------------------------------
 // mwf_wfa_auto() (miniwfa.c:824-834): when the exact WFA passes 1e8 wavefront cells, mwf_wfa_chain() (miniwfa.c:776-822) anchors the
@@ -262,8 +280,7 @@ __global__ void __launch_bounds__(256) k_wfa_mark_pending(int n, mga_wfa_res_t *
 // of stretches; wfachain.c) is integer work on two sequences and runs on the host; the stretches -- all of the DP -- go through the
 // ladder again as ordinary problems (sub-ranges of the same device sequences, no cell cap: miniwfa.c:831), and the stitched
 // CIGAR replaces the result of the problem.  Rare by construction (a gap of tens of kilobases at > 10 % divergence).
-static int wfs_fallback(mga_sctx_t *sc, int n_fb, const int32_t *d_fb, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-						mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used)
+static int wfs_fallback(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n_fb, const int32_t *d_fb)
 {
 	struct job_t { int32_t pi; mga_wfa_prob_t pb; mga_wfa_res_t r0; mga_wc_plan_t plan; int64_t sub0; };
 	if (sc->wfa_uncapped) { mga_set_error("WFA fallback: nested cell cap"); return -1; } // cannot happen: the nested ladder has no cap
@@ -280,9 +297,9 @@ static int wfs_fallback(mga_sctx_t *sc, int n_fb, const int32_t *d_fb, const mga
 	for (int j = 0; j < n_fb; ++j) {
 		job_t &J = job[j];
 		J.pi = ids[j], J.sub0 = (int64_t)sub.size();
-		if (mga_d2h(&J.pb, d_prob + J.pi, sizeof(mga_wfa_prob_t)) < 0 || mga_d2h(&J.r0, d_res + J.pi, sizeof(mga_wfa_res_t)) < 0) goto done;
+		if (mga_d2h(&J.pb, jb->d_prob + J.pi, sizeof(mga_wfa_prob_t)) < 0 || mga_d2h(&J.r0, jb->d_res + J.pi, sizeof(mga_wfa_res_t)) < 0) goto done;
 		tbuf.resize((size_t)J.pb.tl + 1); qbuf.resize((size_t)J.pb.ql + 1);
-		if (mga_d2h(tbuf.data(), d_tseq + J.pb.t_off, (size_t)J.pb.tl) < 0 || mga_d2h(qbuf.data(), d_qseq + J.pb.q_off, (size_t)J.pb.ql) < 0) goto done;
+		if (mga_d2h(tbuf.data(), jb->d_tseq + J.pb.t_off, (size_t)J.pb.tl) < 0 || mga_d2h(qbuf.data(), jb->d_qseq + J.pb.q_off, (size_t)J.pb.ql) < 0) goto done;
 		if (mga_wfa_chain_plan(&par, J.pb.tl, tbuf.data(), J.pb.ql, qbuf.data(), &J.plan) < 0) { mga_set_error("WFA fallback: out of memory"); goto done; }
 		for (int32_t i = 0; i < J.plan.n; ++i) {
 			const mga_wc_el_t &e = J.plan.el[i];
@@ -296,12 +313,13 @@ static int wfs_fallback(mga_sctx_t *sc, int n_fb, const int32_t *d_fb, const mga
 			if (mga_dbuf_reserve(&sc->fb_prob, (size_t)n_sub * sizeof(mga_wfa_prob_t)) < 0 || mga_dbuf_reserve(&sc->fb_res, (size_t)n_sub * sizeof(mga_wfa_res_t)) < 0) goto done;
 			if (mga_h2d(sc->fb_prob.p, sub.data(), (size_t)n_sub * sizeof(mga_wfa_prob_t)) < 0) goto done;
 			sc->wfa_uncapped = 1;
-			const int rc = mga_dev_wfa_solve(sc, n_sub, (const mga_wfa_prob_t*)sc->fb_prob.p, d_tseq, d_qseq, (mga_wfa_res_t*)sc->fb_res.p, d_pool, pool_cap, d_pool_used, 0, 0, 0);
+			const mga_wfa_job_t sub_job = { (const mga_wfa_prob_t*)sc->fb_prob.p, jb->d_tseq, jb->d_qseq, (mga_wfa_res_t*)sc->fb_res.p, jb->d_pool, jb->pool_cap, jb->d_pool_used }; // same sequences and pool, the stretches as the problems
+			const int rc = mga_dev_wfa_solve(sc, &sub_job, n_sub, 0);
 			sc->wfa_uncapped = 0;
 			if (rc < 0 || mga_ssync(sc) < 0 || mga_d2h(sres.data(), sc->fb_res.p, (size_t)n_sub * sizeof(mga_wfa_res_t)) < 0) goto done;
 		}
 		unsigned long long used = 0;
-		if (mga_d2h(&used, d_pool_used, 8) < 0) goto done;
+		if (mga_d2h(&used, jb->d_pool_used, 8) < 0) goto done;
 		std::vector<uint32_t> cig, out;
 		std::vector<const uint32_t*> cptr;
 		std::vector<int32_t> cn;
@@ -314,7 +332,7 @@ static int wfs_fallback(mga_sctx_t *sc, int n_fb, const int32_t *d_fb, const mga
 			tot = 0;
 			for (int64_t k = J.sub0; k < s1; ++k) {
 				if (sres[k].status != MGA_WFA_OK) { mga_set_error("WFA fallback: sub-problem failed (status %d)", sres[k].status); goto done; }
-				if (sres[k].n_cigar > 0 && mga_d2h(cig.data() + tot, d_pool + sres[k].cig_off, (size_t)sres[k].n_cigar * 4) < 0) goto done;
+				if (sres[k].n_cigar > 0 && mga_d2h(cig.data() + tot, jb->d_pool + sres[k].cig_off, (size_t)sres[k].n_cigar * 4) < 0) goto done;
 				cptr.push_back(cig.data() + tot); cn.push_back(sres[k].n_cigar);
 				tot += sres[k].n_cigar, iter += sres[k].n_iter, score += sres[k].score;
 			}
@@ -322,14 +340,14 @@ static int wfs_fallback(mga_sctx_t *sc, int n_fb, const int32_t *d_fb, const mga
 			out.resize((size_t)cap);
 			const int64_t n_out = mga_wfa_chain_stitch(&J.plan, cptr.data(), cn.data(), out.data(), cap);
 			if (n_out < 0) { mga_set_error("WFA fallback: stitch overflow"); goto done; }
-			if ((int64_t)used + n_out > pool_cap) { mga_set_error("WFA fallback: CIGAR pool of %ld ops exhausted", (long)pool_cap); goto done; }
+			if ((int64_t)used + n_out > jb->pool_cap) { mga_set_error("WFA fallback: CIGAR pool of %ld ops exhausted", (long)jb->pool_cap); goto done; }
 			mga_wfa_res_t r;
 			r.score = (int32_t)score, r.n_cigar = (int32_t)n_out, r.cig_off = (int64_t)used, r.status = MGA_WFA_OK, r.pad = 0, r.n_iter = iter;
-			if (n_out > 0 && mga_h2d(d_pool + used, out.data(), (size_t)n_out * 4) < 0) goto done;
-			if (mga_h2d(d_res + J.pi, &r, sizeof(r)) < 0) goto done;
+			if (n_out > 0 && mga_h2d(jb->d_pool + used, out.data(), (size_t)n_out * 4) < 0) goto done;
+			if (mga_h2d(jb->d_res + J.pi, &r, sizeof(r)) < 0) goto done;
 			used += (unsigned long long)n_out;
 		}
-		if (mga_h2d(d_pool_used, &used, 8) < 0) goto done;
+		if (mga_h2d(jb->d_pool_used, &used, 8) < 0) goto done;
 	}
 	ret = 0;
 done:
@@ -350,25 +368,17 @@ extern "C" void mga_wfa_ladder_stats(int64_t *launched, int64_t *given_up, int r
 // The rung behind the ladder (k_wfa_seg.hip): the stretches of the chained fallback that outgrew the last HBM tier are closed in the reference's low-memory mode
 // (miniwfa.c:440-601), whose memory the host sizes per problem.  They are the problems a finished sweep leaves with MGA_WFA_RETRY_TIER; a handful at most, so the
 // host reads their descriptors back in one copy.  What cannot be placed even there fails with the computed figure (mga_dev_wfa_seg).
-static int wfs_seg_rung(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap,
-						unsigned long long *d_pool_used, int *d_cnt /* two free words of the control block */)
+static int wfs_seg_rung(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, int *d_cnt /* two free words of the control block */)
 {
-	hipStream_t st = (hipStream_t)sc->stream;
-	int k = 0;
-	if (mga_dbuf_reserve(&sc->wfa_list[1], (size_t)n * 4 + 64) < 0) return -1;
-	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
-	hipLaunchKernelGGL(k_wfa_collect_open, dim3((n + 255) / 256), dim3(256), 0, st, n, (const mga_wfa_res_t*)d_res, (int32_t*)sc->wfa_list[1].p, d_cnt);
-	MGA_HIP_CHECK(hipGetLastError());
-	if (mga_d2h_s(sc, &k, d_cnt, 4) < 0 || mga_ssync(sc) < 0) return -1;
-	MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
-	if (k <= 0) return 0;
+	const int k = wfs_collect_open(sc, n, job->d_res, d_cnt);
+	if (k <= 0) return k;
 	std::vector<int32_t> ids((size_t)k), tl((size_t)k), ql((size_t)k);
 	if (mga_d2h(ids.data(), sc->wfa_list[1].p, (size_t)k * 4) < 0) return -1;
 	std::sort(ids.begin(), ids.end()); // (collected in completion order; the pool's layout should not depend on it)
 	std::vector<mga_wfa_prob_t> pb((size_t)(ids[k - 1] - ids[0] + 1)); // the uncapped ladder's problems are the few stretches of a fallback: one copy of the span that holds them
-	if (mga_d2h(pb.data(), d_prob + ids[0], pb.size() * sizeof(mga_wfa_prob_t)) < 0) return -1;
+	if (mga_d2h(pb.data(), job->d_prob + ids[0], pb.size() * sizeof(mga_wfa_prob_t)) < 0) return -1;
 	for (int j = 0; j < k; ++j) tl[j] = pb[ids[j] - ids[0]].tl, ql[j] = pb[ids[j] - ids[0]].ql;
-	return mga_dev_wfa_seg(sc, k, ids.data(), tl.data(), ql.data(), 0, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used);
+	return mga_dev_wfa_seg(sc, job, k, ids.data(), tl.data(), ql.data(), 0);
 }
 
 // One SWEEP of the ladder (round 3): the rungs run ONCE each, in ascending order, on the context's stream.  A problem that gives up on rung t is appended to
@@ -377,132 +387,156 @@ static int wfs_seg_rung(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_prob, con
 // synchronisations and ~3 launches per rung and chunk, [measured] 79 ms per 125k reads in the 512-diagonal tier alone, most of it launch tails).
 // A rung's list has room for its own problems + a share of what the rungs below it run; an overflow (never seen on real reads) only moves the count on, and
 // the host then sweeps once more over what is still open.
-static int wfs_sweep(mga_sctx_t *sc, const wfs_ladder_t *LD, int arr_pct, int n_list, const int32_t *d_ids /* NULL: problems 0 .. n_list - 1 */,
-					 const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap,
-					 unsigned long long *d_pool_used, int *ctl, bool *any_tb, int *n_open, int *n_over /* problems that fell off the last rung (uncapped ladder only: elsewhere an error) */)
+// The state of one sweep; its stages, below in the order wfs_sweep() calls them, fill it from top to bottom.
+constexpr int NS = MGA_WFA_N_SLOT;
+struct wfs_sweep_t {
+	mga_sctx_t *sc; const wfs_ladder_t *LD; const mga_wfa_job_t *job; wfs_ctl_t *ctl; hipStream_t st; // (st: the context's stream)
+	int arr_pct, n_list, n_stable, dbg; const int32_t *d_ids; // the problems swept: d_ids[0 .. n_list) (NULL: problems 0 .. n_list - 1); MGA_WFA_LIST_STABLE as it applies to this ladder, MGA_DEBUG_WFA
+	int toff[NS + 2];                                  // wfs_bin: first slot of every rung in the compact order
+	int *own, cap[NS], base[NS + 1]; int32_t *L;       // wfs_size_lists: per rung its own problems (sc->wfa_own), the room of its list and that list's first slot in L (sc->wfa_list[0])
+	int64_t tb_bytes;                                  //   traceback regions: ONE buffer, the largest windowed rung's -- every rung's walk (k_wfa_tb) runs right behind its forward pass
+	hipStream_t side; bool use_side, forked;           // wfs_own_rungs: the stream of the register / HBM rungs' own problems (st with MGA_WFA_SIDE=0); forked: it waits for the binning (or is st)
+};
+
+// every problem's key (first rung, length bin), the histogram of the keys, the rungs' first slots in the compact order
+static int wfs_bin(wfs_sweep_t &S)
 {
-	constexpr int NS = MGA_WFA_N_SLOT;
-	constexpr int O_TOFF = WFS_NBIN, O_RC = O_TOFF + 16, O_ERR = O_RC + 32;
-	hipStream_t st = (hipStream_t)sc->stream;
-	const int NR = LD->n;
-	static int dbg = -1;
-	if (dbg < 0) { const char *e = getenv("MGA_DEBUG_WFA"); dbg = e && atoi(e) > 0; }
-	*n_open = 0;
-	// MGA_WFA_LIST_STABLE=<n>: the lists of the first n windowed rungs in problem order (k_wfa_bin_scatter); 0 (default) = every rung longest-first.  [measured, profiles/r05r_list_sweep.txt]
-	// n = 3: W16 12.7 -> 12.0, W32 15.1 -> 15.5, the traceback walk 18.0 -> 17.8-18.0 ms per 125 000 reads: the walk is a chain of dependent loads per lane, not their volume.  Only the new ladder's
-	// narrow rungs qualify (the old ladder's rungs are multi-wave kernels whose launches do end in their longest problems)
-	static int n_stable_env = -1;
-	if (n_stable_env < 0) { const char *e = getenv("MGA_WFA_LIST_STABLE"); n_stable_env = e && *e ? atoi(e) : 0; if (n_stable_env > 3) n_stable_env = 3; if (n_stable_env < 0) n_stable_env = 0; }
-	const int n_stable = LD->r[0].kind != 0 ? 0 : n_stable_env; // (kind 1: the round-2 ladder, register tiers from the first rung on)
-	MGA_HIP_CHECK(hipMemsetAsync(ctl, 0, (size_t)O_ERR * 4, st)); // histogram, offsets, list lengths (the err / fb / cells words behind them are kept)
-	{
-		int nb = (n_list + 1023) / 1024;
-		if (nb > 1024) nb = 1024;
-		wfs_thr_t T;
-		T.n = NR, T.n_stable = n_stable;
-		for (int k = 0; k < NS; ++k) T.t[k] = k < NR ? LD->r[k].maxlen : 0x7fffffff;
-		mga_prof_begin(st, MGA_K_SCAN);
-		hipLaunchKernelGGL(k_wfa_bin_count, dim3(nb), dim3(1024), 0, st, n_list, d_ids, d_prob, (int32_t*)sc->wfa_key.p, ctl, T);
-		hipLaunchKernelGGL(k_wfa_bin_scan, dim3(1), dim3(1024), 0, st, ctl, ctl + O_TOFF);
-		mga_prof_end(st, MGA_K_SCAN);
-		MGA_HIP_CHECK(hipGetLastError());
+	const int nb = std::min((S.n_list + 1023) / 1024, 1024);
+	MGA_HIP_CHECK(hipMemsetAsync(S.ctl, 0, offsetof(wfs_ctl_t, err), S.st)); // histogram, offsets, list lengths (the err / fb / cells words behind them are kept)
+	wfs_thr_t T; T.n = S.LD->n, T.n_stable = S.n_stable;
+	for (int k = 0; k < NS; ++k) T.t[k] = k < T.n ? S.LD->r[k].maxlen : 0x7fffffff;
+	mga_prof_begin(S.st, MGA_K_SCAN);
+	hipLaunchKernelGGL(k_wfa_bin_count, dim3(nb), dim3(1024), 0, S.st, S.n_list, S.d_ids, S.job->d_prob, (int32_t*)S.sc->wfa_key.p, S.ctl->hist, T);
+	hipLaunchKernelGGL(k_wfa_bin_scan, dim3(1), dim3(1024), 0, S.st, S.ctl->hist, S.ctl->tier_off);
+	mga_prof_end(S.st, MGA_K_SCAN);
+	MGA_HIP_CHECK(hipGetLastError());
+	return mga_d2h_s(S.sc, S.toff, S.ctl->tier_off, (NS + 1) * 4) < 0 || mga_ssync(S.sc) < 0 ? -1 : 0;
+}
+
+// the rungs' lists: sized, filled with their own problems (k_wfa_bin_scatter), their lengths and the launches' counters set
+static int wfs_size_lists(wfs_sweep_t &S)
+{
+	mga_sctx_t *sc = S.sc; const wfs_ladder_t *LD = S.LD;
+	const int NR = LD->n, arr_pct = S.arr_pct, n_list = S.n_list, *h = S.toff;
+	int *own = S.own = sc->wfa_own, *cap = S.cap, *base = S.base; // (own lives in the context: the copy engine reads it after this frame's locals could be gone)
+	int64_t feed[NS]; // room of every rung's list: its own problems + arr_pct % of what the rungs feeding it may run (+ 4096)
+	for (int t = 0; t < NS; ++t) own[t] = t < NR ? h[t + 1] - h[t] : 0, feed[t] = 0, cap[t] = 0;
+	for (int t = 0; t < NR; ++t) {
+		int64_t c = own[t] + (feed[t] > 0 ? feed[t] * arr_pct / 100 + (arr_pct < 100 ? 4096 : 0) : 0);
+		if (c > n_list) c = n_list;
+		cap[t] = (int)c;
+		if (LD->r[t].next >= 0) feed[LD->r[t].next] += c;
 	}
-	int h[NS + 2], cap[NS], base[NS + 1];
-	int *own = sc->wfa_own; // (lives in the context: the copy engine reads it after this frame's locals could be gone)
-	if (mga_d2h_s(sc, h, ctl + O_TOFF, (NS + 1) * 4) < 0 || mga_ssync(sc) < 0) return -1;
-	int64_t tot_cap = 0;
-	{ // room of every rung's list: its own problems + arr_pct % of what the rungs feeding it may run (+ 4096)
-		int64_t feed[NS];
-		for (int t = 0; t < NS; ++t) own[t] = t < NR ? h[t + 1] - h[t] : 0, feed[t] = 0;
-		for (int t = 0; t < NR; ++t) {
-			int64_t c = own[t] + (feed[t] > 0 ? feed[t] * arr_pct / 100 + (arr_pct < 100 ? 4096 : 0) : 0);
-			if (c > n_list) c = n_list;
-			cap[t] = (int)c;
-			if (LD->r[t].next >= 0) feed[LD->r[t].next] += c;
-		}
-		for (int t = NR; t < NS; ++t) cap[t] = 0;
-		base[0] = 0;
-		for (int t = 0; t < NS; ++t) base[t + 1] = base[t] + cap[t], tot_cap = base[t + 1];
-	}
-	if (mga_dbuf_reserve(&sc->wfa_list[0], (size_t)tot_cap * 4 + 64) < 0) return -1;
-	int32_t *L = (int32_t*)sc->wfa_list[0].p;
-	{
-		wfs_shift_t sh;
-		for (int t = 0; t < NS; ++t) sh.s[t] = t < NR ? base[t] - h[t] : 0;
-		mga_prof_begin(st, MGA_K_SCAN);
-		hipLaunchKernelGGL(k_wfa_bin_scatter, dim3((n_list + 8191) / 8192), dim3(1024), 0, st, n_list, d_ids, (const int32_t*)sc->wfa_key.p, ctl, L, sh, n_stable);
-		mga_prof_end(st, MGA_K_SCAN);
-		MGA_HIP_CHECK(hipGetLastError());
-	}
-	int *rc = ctl + O_RC; // rc[t]: length of rung t's list (own problems, then arrivals); rc[15]: problems beyond the last rung
-	MGA_HIP_CHECK(hipMemcpyAsync(rc, own, NS * 4, hipMemcpyHostToDevice, st));
-	MGA_HIP_CHECK(hipMemsetAsync(sc->wfa_cnt.p, 0, 4096, st)); // the launches' work-queue counters (one 64-byte line each)
-	int64_t tb_bytes = 0; // traceback regions: ONE buffer, the largest windowed rung's -- every rung's walk (k_wfa_tb) runs right behind its forward pass
-	for (int t = 0; t < NR; ++t) if (LD->r[t].kind == 0 && cap[t] > 0 && (int64_t)cap[t] * mga_dev_wfa_win_tb_stride(LD->r[t].idx) > tb_bytes) tb_bytes = (int64_t)cap[t] * mga_dev_wfa_win_tb_stride(LD->r[t].idx);
-	if (tb_bytes > 0 && mga_dbuf_reserve(&sc->wfa_tbuf[0], (size_t)tb_bytes + 256) < 0) return -1;
-	(void)any_tb;
-	// The register / HBM rungs hold few, long problems (hundreds to thousands of score steps each: a launch is as long as its longest chain of them, with most of
-	// the GPU idle).  Their OWN problems depend on nothing, so they start NOW on a side stream, next to the windowed rungs that fill the machine; what ARRIVES
-	// at them from below is run by a second, short launch at the end of the sweep ([measured] 68 ms of the 225 ms of an isolated WFA phase were these tails).
+	base[0] = 0;
+	for (int t = 0; t < NS; ++t) base[t + 1] = base[t] + cap[t];
+	if (mga_dbuf_reserve(&sc->wfa_list[0], (size_t)base[NS] * 4 + 64) < 0) return -1;
+	S.L = (int32_t*)sc->wfa_list[0].p;
+	wfs_shift_t sh; // (the scatter's cursors are in the compact order)
+	for (int t = 0; t < NS; ++t) sh.s[t] = t < NR ? base[t] - h[t] : 0;
+	mga_prof_begin(S.st, MGA_K_SCAN);
+	hipLaunchKernelGGL(k_wfa_bin_scatter, dim3((n_list + 8191) / 8192), dim3(1024), 0, S.st, n_list, S.d_ids, (const int32_t*)sc->wfa_key.p, S.ctl->hist, S.L, sh, S.n_stable);
+	mga_prof_end(S.st, MGA_K_SCAN);
+	MGA_HIP_CHECK(hipGetLastError());
+	MGA_HIP_CHECK(hipMemcpyAsync(S.ctl->rc, own, NS * 4, hipMemcpyHostToDevice, S.st));
+	MGA_HIP_CHECK(hipMemsetAsync(sc->wfa_cnt.p, 0, 4096, S.st)); // the launches' work-queue counters (one 64-byte line each)
+	for (int t = 0; t < NR; ++t) if (LD->r[t].kind == 0 && cap[t] > 0 && (int64_t)cap[t] * mga_dev_wfa_win_tb_stride(LD->r[t].idx) > S.tb_bytes) S.tb_bytes = (int64_t)cap[t] * mga_dev_wfa_win_tb_stride(LD->r[t].idx);
+	return S.tb_bytes > 0 && mga_dbuf_reserve(&sc->wfa_tbuf[0], (size_t)S.tb_bytes + 256) < 0 ? -1 : 0;
+}
+
+// the launch of rung t over list entries first .. cap; what the rung gives up goes to the rung after it (past the last rung: only counted)
+static mga_wfa_launch_t wfs_launch(const wfs_sweep_t &S, int t, int first, int cap, int slot, hipStream_t stream)
+{
+	const int nx = S.LD->r[t].next; // (wfa_fb takes the problems that hit the cell cap: only the HBM tiers count cells)
+	const mga_wfa_retry_t rt = { nx >= 0 ? S.L + S.base[nx] : S.L, S.ctl->rc + (nx >= 0 ? nx : WFS_RC_OVER), &S.ctl->err, (int32_t*)S.sc->wfa_fb.p, &S.ctl->fb, nx >= 0 ? S.cap[nx] : 0 };
+	return mga_wfa_launch_t{ S.ctl->rc + t, cap, first, S.L + S.base[t], slot, (void*)stream, rt };
+}
+
+// The register / HBM rungs hold few, long problems (hundreds to thousands of score steps each: a launch is as long as its longest chain of them, with most of
+// the GPU idle).  Their OWN problems depend on nothing, so they start NOW on a side stream, next to the windowed rungs that fill the machine; what ARRIVES
+// at them from below is run by a second, short launch at the end of the sweep ([measured] 68 ms of the 225 ms of an isolated WFA phase were these tails).
+static int wfs_own_rungs(wfs_sweep_t &S)
+{
+	const wfs_ladder_t *LD = S.LD;
 	const char *e_side = getenv("MGA_WFA_SIDE");
-	const int use_side = !(e_side && atoi(e_side) == 0); // MGA_WFA_SIDE=0: everything on one stream (bench.py's isolated pass: per-kernel timings that do not overlap)
-	hipStream_t side = use_side ? (hipStream_t)sc->tier_stream[0] : st;
-	bool forked = !use_side;
-	auto rt_of = [&](int t) {
-		const int nx = LD->r[t].next;
-		// (wfa_fb takes the problems that hit the cell cap: only the HBM tiers count cells)
-		return mga_wfa_retry_t{ nx >= 0 ? L + base[nx] : L, rc + (nx >= 0 ? nx : 15), ctl + O_ERR, (int32_t*)sc->wfa_fb.p, ctl + O_ERR + 1, nx >= 0 ? cap[nx] : 0 };
-	};
-	for (int t = 0; t < NR; ++t) {
-		if (LD->r[t].kind != 1 || own[t] <= 0) continue;
-		if (!forked) {
-			MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_ready, st));
-			MGA_HIP_CHECK(hipStreamWaitEvent(side, (hipEvent_t)sc->ev_ready, 0));
-			forked = true;
+	S.use_side = !(e_side && atoi(e_side) == 0); // MGA_WFA_SIDE=0: everything on one stream (bench.py's isolated pass: per-kernel timings that do not overlap)
+	S.side = S.use_side ? (hipStream_t)S.sc->tier_stream[0] : S.st;
+	S.forked = !S.use_side;
+	for (int t = 0; t < LD->n; ++t) {
+		if (LD->r[t].kind != 1 || S.own[t] <= 0) continue;
+		if (!S.forked) {
+			MGA_HIP_CHECK(hipEventRecord((hipEvent_t)S.sc->ev_ready, S.st));
+			MGA_HIP_CHECK(hipStreamWaitEvent(S.side, (hipEvent_t)S.sc->ev_ready, 0));
+			S.forked = true;
 		}
-		if (mga_dev_wfa_tier(sc, rc + t, own[t], 0, LD->r[t].idx, side, L + base[t], d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, LD->r[t].idx, rt_of(t)) < 0) return -1;
+		const mga_wfa_launch_t ln = wfs_launch(S, t, 0, S.own[t], WFS_CNT_OWN + LD->r[t].idx, S.side);
+		if (mga_dev_wfa_tier(S.sc, S.job, &ln, LD->r[t].idx) < 0) return -1;
 	}
-	// Round 5: a rung's walk (k_wfa_tb: a lane per problem chasing traceback bytes -- bound by memory latency, 2 % of the vector issue slots) runs on a stream of its own
-	// NEXT TO the following rung's forward pass (bound by vector issue): two traceback buffers used in turn, the forward pass of rung k waits for the walk of rung
-	// k - 2 (the previous user of its buffer), the walk of rung k for its forward pass.  Opt-in (MGA_WFA_TB_SIDE=1): measured, no gain -- see below; the default and the isolated pass (MGA_WFA_SIDE=0) use one buffer, one stream.
+	return 0;
+}
+
+// The windowed rungs, each followed by its walk.  Round 5: a rung's walk (k_wfa_tb: a lane per problem chasing traceback bytes -- bound by memory latency, 2 % of the vector issue slots) runs on a stream of its own
+// NEXT TO the following rung's forward pass (bound by vector issue): two traceback buffers used in turn, the forward pass of rung k waits for the walk of rung
+// k - 2 (the previous user of its buffer), the walk of rung k for its forward pass.  Opt-in (MGA_WFA_TB_SIDE=1): measured, no gain -- see below; the default and the isolated pass (MGA_WFA_SIDE=0) use one buffer, one stream.
+static int wfs_win_rungs(wfs_sweep_t &S)
+{
+	mga_sctx_t *sc = S.sc; const wfs_ladder_t *LD = S.LD; hipStream_t st = S.st;
 	const char *e_tbs = getenv("MGA_WFA_TB_SIDE");
-	const bool tb_side = use_side && e_tbs && atoi(e_tbs) > 0; // [measured, round 5, bench workload, three interleaved repetitions] 3.51 / 3.60 / 3.36 Gbp/s with the walk on its own stream against 3.61 / 3.63 without: kept behind MGA_WFA_TB_SIDE=1, not the default
-	hipStream_t tbs = tb_side ? (hipStream_t)sc->tier_stream[1] : st;
-	if (tb_side && tb_bytes > 0 && mga_dbuf_reserve(&sc->wfa_tbuf[1], (size_t)tb_bytes + 256) < 0) return -1;
+	const bool tb_side = S.use_side && e_tbs && atoi(e_tbs) > 0; // [measured, round 5, bench workload, three interleaved repetitions] 3.51 / 3.60 / 3.36 Gbp/s with the walk on its own stream against 3.61 / 3.63 without: kept behind MGA_WFA_TB_SIDE=1, not the default
+	hipStream_t walk = tb_side ? (hipStream_t)sc->tier_stream[1] : st; // the stream of the walks
+	if (tb_side && S.tb_bytes > 0 && mga_dbuf_reserve(&sc->wfa_tbuf[1], (size_t)S.tb_bytes + 256) < 0) return -1;
 	int n_win = 0;
-	for (int t = 0; t < NR; ++t) {
-		if (LD->r[t].kind != 0 || cap[t] <= 0) continue;
+	for (int t = 0; t < LD->n; ++t) {
+		if (LD->r[t].kind != 0 || S.cap[t] <= 0) continue;
+		const int wt = LD->r[t].idx;
 		char *tbuf = (char*)sc->wfa_tbuf[tb_side ? (n_win & 1) : 0].p;
+		mga_wfa_launch_t ln = wfs_launch(S, t, 0, S.cap[t], WFS_CNT_WIN + wt, st); // the forward pass; its walk takes the same list on the stream of the walks
 		if (tb_side && n_win >= 2) MGA_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)sc->ev_done[2 + (n_win & 1)], 0)); // the walk that read this buffer two rungs ago
-		if (mga_dev_wfa_win(sc, rc + t, cap[t], L + base[t], d_prob, d_tseq, d_qseq, d_res, tbuf, LD->r[t].idx, 9 + LD->r[t].idx, rt_of(t), d_pool, pool_cap, d_pool_used, ctl + O_ERR) < 0) return -1;
+		if (mga_dev_wfa_win(sc, S.job, &ln, tbuf, wt, &S.ctl->err) < 0) return -1;
 		if (tb_side) {
 			MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_done[1], st));
-			MGA_HIP_CHECK(hipStreamWaitEvent(tbs, (hipEvent_t)sc->ev_done[1], 0));
+			MGA_HIP_CHECK(hipStreamWaitEvent(walk, (hipEvent_t)sc->ev_done[1], 0));
 		}
-		if (mga_dev_wfa_traceback(sc, tbs, rc + t, cap[t], L + base[t], d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl + O_ERR, LD->r[t].idx) < 0) return -1;
-		if (tb_side) MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_done[2 + (n_win & 1)], tbs));
+		ln.stream = (void*)walk;
+		if (mga_dev_wfa_traceback(sc, S.job, &ln, &S.ctl->err, wt) < 0) return -1;
+		if (tb_side) MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_done[2 + (n_win & 1)], walk));
 		++n_win;
 	}
 	if (tb_side) for (int k = 0; k < 2 && k < n_win; ++k) MGA_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)sc->ev_done[2 + k], 0)); // every walk is through before what follows on the main stream
-	if (forked && use_side) {
-		MGA_HIP_CHECK(hipEventRecord((hipEvent_t)sc->ev_done[0], side));
-		MGA_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)sc->ev_done[0], 0));
+	return 0;
+}
+
+// arrivals at the register / HBM rungs, in ascending order (a rung's own launch may itself have sent problems up), once the side stream is through
+static int wfs_arrivals(wfs_sweep_t &S)
+{
+	const wfs_ladder_t *LD = S.LD;
+	if (S.forked && S.use_side) {
+		MGA_HIP_CHECK(hipEventRecord((hipEvent_t)S.sc->ev_done[0], S.side));
+		MGA_HIP_CHECK(hipStreamWaitEvent(S.st, (hipEvent_t)S.sc->ev_done[0], 0));
 	}
-	for (int t = 0; t < NR; ++t) { // arrivals at the register / HBM rungs, in ascending order (a rung's own launch may itself have sent problems up)
-		if (LD->r[t].kind != 1 || cap[t] - own[t] <= 0) continue;
-		if (mga_dev_wfa_tier(sc, rc + t, cap[t], own[t], 32 + LD->r[t].idx, 0, L + base[t], d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, LD->r[t].idx, rt_of(t)) < 0) return -1;
+	for (int t = 0; t < LD->n; ++t) {
+		if (LD->r[t].kind != 1 || S.cap[t] - S.own[t] <= 0) continue;
+		const mga_wfa_launch_t ln = wfs_launch(S, t, S.own[t], S.cap[t], WFS_CNT_ARR + LD->r[t].idx, S.st);
+		if (mga_dev_wfa_tier(S.sc, S.job, &ln, LD->r[t].idx) < 0) return -1;
 	}
+	return 0;
+}
+
+// the rungs' final list lengths read back and accounted: *n_open = problems whose rung's list was full, *n_over += problems that fell off the last rung (uncapped ladder only: elsewhere an error)
+static int wfs_account(wfs_sweep_t &S, int *n_open, int *n_over)
+{
+	mga_sctx_t *sc = S.sc; const wfs_ladder_t *LD = S.LD;
+	const int NR = LD->n, *own = S.own, *cap = S.cap;
 	int hr[16], herr = 0;
-	if (mga_d2h_s(sc, hr, rc, 16 * 4) < 0 || mga_d2h_s(sc, &herr, ctl + O_ERR, 4) < 0 || mga_ssync(sc) < 0) return -1;
-	if (dbg) {
-		fprintf(stderr, "[wfa] sweep over %d problems:", n_list);
+	if (mga_d2h_s(sc, hr, S.ctl->rc, 16 * 4) < 0 || mga_d2h_s(sc, &herr, &S.ctl->err, 4) < 0 || mga_ssync(sc) < 0) return -1;
+	if (S.dbg) {
+		fprintf(stderr, "[wfa] sweep over %d problems:", S.n_list);
 		for (int t = 0; t < NR; ++t) if (hr[t]) fprintf(stderr, " %s%d: %d (+%d, room %d)", LD->r[t].kind == 0 ? "W" : "R", LD->r[t].idx, own[t], hr[t] - own[t], cap[t]);
 		fprintf(stderr, "\n");
 	}
-	if (herr) { mga_set_error("WFA: %d problems failed (CIGAR pool of %ld ops exhausted, iteration cap, or a traceback walked out of its window)", herr, (long)pool_cap); return -1; }
-	if (hr[15] > 0) {
-		if (!sc->wfa_uncapped) { mga_set_error("%d WFA problems exceed the largest capacity tier", hr[15]); return -1; }
-		*n_over += hr[15]; // their status is MGA_WFA_RETRY_TIER: the low-memory rung takes them after the sweeps (wfs_seg_rung)
+	if (herr) { mga_set_error("WFA: %d problems failed (CIGAR pool of %ld ops exhausted, iteration cap, or a traceback walked out of its window)", herr, (long)S.job->pool_cap); return -1; }
+	if (hr[WFS_RC_OVER] > 0) {
+		if (!sc->wfa_uncapped) { mga_set_error("%d WFA problems exceed the largest capacity tier", hr[WFS_RC_OVER]); return -1; }
+		*n_over += hr[WFS_RC_OVER]; // their status is MGA_WFA_RETRY_TIER: the low-memory rung takes them after the sweeps (wfs_seg_rung)
 	}
 	if (!sc->wfa_uncapped) for (int t = 0; t < NR; ++t) {
 		__atomic_fetch_add(&g_rung_n[t], (long long)(hr[t] < cap[t] ? hr[t] : cap[t]), __ATOMIC_RELAXED);
@@ -512,57 +546,62 @@ static int wfs_sweep(mga_sctx_t *sc, const wfs_ladder_t *LD, int arr_pct, int n_
 	return 0;
 }
 
-extern "C" int mga_dev_wfa_solve(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-								 mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int64_t *cells,
-								 void (*bulk_done)(void*), void *bulk_arg)
+static int wfs_sweep(mga_sctx_t *sc, const wfs_ladder_t *LD, const mga_wfa_job_t *job, int arr_pct, int n_list, const int32_t *d_ids /* NULL: problems 0 .. n_list - 1 */, int *n_open, int *n_over)
 {
-	(void)bulk_done; (void)bulk_arg; // (round 2: early release of the caller's GPU-phase token between concurrent tiers; a sweep is one chain of launches)
+	static int dbg = -1;
+	if (dbg < 0) { const char *e = getenv("MGA_DEBUG_WFA"); dbg = e && atoi(e) > 0; }
+	*n_open = 0;
+	// MGA_WFA_LIST_STABLE=<n>: the lists of the first n windowed rungs in problem order (k_wfa_bin_scatter); 0 (default) = every rung longest-first.  [measured, profiles/r05r_list_sweep.txt]
+	// n = 3: W16 12.7 -> 12.0, W32 15.1 -> 15.5, the traceback walk 18.0 -> 17.8-18.0 ms per 125 000 reads: the walk is a chain of dependent loads per lane, not their volume.  Only the new ladder's
+	// narrow rungs qualify (the old ladder's rungs are multi-wave kernels whose launches do end in their longest problems)
+	static int n_stable_env = -1;
+	if (n_stable_env < 0) { const char *e = getenv("MGA_WFA_LIST_STABLE"); n_stable_env = e && *e ? atoi(e) : 0; if (n_stable_env > 3) n_stable_env = 3; if (n_stable_env < 0) n_stable_env = 0; }
+	wfs_sweep_t S = {}; S.sc = sc, S.LD = LD, S.job = job, S.ctl = (wfs_ctl_t*)sc->wfa_ctl.p /* (reserved and zeroed by mga_dev_wfa_solve) */, S.arr_pct = arr_pct, S.n_list = n_list, S.d_ids = d_ids, S.dbg = dbg, S.st = (hipStream_t)sc->stream;
+	S.n_stable = LD->r[0].kind != 0 ? 0 : n_stable_env; // (kind 1: the round-2 ladder, register tiers from the first rung on)
+	if (wfs_bin(S) < 0 || wfs_size_lists(S) < 0 || wfs_own_rungs(S) < 0 || wfs_win_rungs(S) < 0 || wfs_arrivals(S) < 0) return -1;
+	return wfs_account(S, n_open, n_over);
+}
+
+extern "C" int mga_dev_wfa_solve(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, int64_t *cells)
+{
 	if (cells) *cells = 0;
 	if (n <= 0) return 0;
 	hipStream_t st = (hipStream_t)sc->stream;
 	const wfs_ladder_t *LD = wfs_ladder(sc->wfa_uncapped); // (the fallback's sub-problems: register / HBM tiers only, results in the pool at once)
-	// ctl: hist[NBIN] | tier_off[16] | rc[2][16] | err | fb | cells (8 bytes)
-	constexpr int O_TOFF = WFS_NBIN, O_RC = O_TOFF + 16, O_ERR = O_RC + 32, O_FB = O_ERR + 1, O_CELLS = O_ERR + 2, N_CTL = O_CELLS + 2;
-	if (mga_dbuf_reserve(&sc->wfa_key, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&sc->wfa_fb, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&sc->wfa_ctl, (size_t)N_CTL * 4) < 0 ||
+	if (mga_dbuf_reserve(&sc->wfa_key, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&sc->wfa_fb, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&sc->wfa_ctl, sizeof(wfs_ctl_t)) < 0 ||
 		mga_dbuf_reserve(&sc->wfa_cnt, 4096) < 0) return -1;
-	int *ctl = (int*)sc->wfa_ctl.p;
-	MGA_HIP_CHECK(hipMemsetAsync(ctl, 0, (size_t)N_CTL * 4, st));
-	hipLaunchKernelGGL(k_wfa_mark_pending, dim3((n + 255) / 256), dim3(256), 0, st, n, d_res);
+	wfs_ctl_t *ctl = (wfs_ctl_t*)sc->wfa_ctl.p;
+	MGA_HIP_CHECK(hipMemsetAsync(ctl, 0, sizeof(wfs_ctl_t), st));
+	hipLaunchKernelGGL(k_wfa_mark_pending, dim3((n + 255) / 256), dim3(256), 0, st, n, job->d_res);
 	MGA_HIP_CHECK(hipGetLastError());
-	bool any_tb = false;
 	int n_open = 0, n_over = 0;
 	static int arr_pct = -1;
 	if (arr_pct < 0) { const char *e = getenv("MGA_WFA_ARRIVALS_PCT"); arr_pct = e ? atoi(e) : 20; } // (tests: 0 leaves a rung's list room for 4096 arrivals only)
-	if (wfs_sweep(sc, LD, arr_pct, n, 0, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open, &n_over) < 0) return -1;
+	if (wfs_sweep(sc, LD, job, arr_pct, n, 0, &n_open, &n_over) < 0) return -1;
 	if (n_open > 0) { // a rung's list overflowed (far more of a chunk's gaps gave up than any read set has shown): what is still open is swept again in slices whose
 		// lists have room for EVERYTHING below them (no second overflow), small enough for the traceback regions that implies
 		const int SLICE = 32768;
-		int *d_cnt = ctl + O_CELLS, k = 0; // (the cells words are free until the end)
-		if (mga_dbuf_reserve(&sc->wfa_list[1], (size_t)n * 4 + 64) < 0) return -1;
-		MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
-		hipLaunchKernelGGL(k_wfa_collect_open, dim3((n + 255) / 256), dim3(256), 0, st, n, (const mga_wfa_res_t*)d_res, (int32_t*)sc->wfa_list[1].p, d_cnt);
-		MGA_HIP_CHECK(hipGetLastError());
-		if (mga_d2h_s(sc, &k, d_cnt, 4) < 0 || mga_ssync(sc) < 0) return -1;
-		MGA_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, st));
+		const int k = wfs_collect_open(sc, n, job->d_res, ctl->cells); // (the cells words are free until the end)
+		if (k < 0) return -1;
 		for (int o = 0; o < k; o += SLICE) {
-			if (wfs_sweep(sc, LD, 100, k - o < SLICE ? k - o : SLICE, (const int32_t*)sc->wfa_list[1].p + o, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl, &any_tb, &n_open, &n_over) < 0) return -1;
+			if (wfs_sweep(sc, LD, job, 100, k - o < SLICE ? k - o : SLICE, (const int32_t*)sc->wfa_list[1].p + o, &n_open, &n_over) < 0) return -1;
 			if (n_open > 0) { mga_set_error("WFA ladder: %d problems open after a sweep with room for all", n_open); return -1; }
 		}
 	}
-	if (n_over > 0 && wfs_seg_rung(sc, n, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used, ctl + O_CELLS) < 0) return -1;
+	if (n_over > 0 && wfs_seg_rung(sc, job, n, ctl->cells) < 0) return -1;
 	{ // problems the exact pass gave up on (> 1e8 cells): miniwfa's chained fallback (miniwfa.c:829-832)
 		int n_fb = 0;
-		if (mga_d2h_s(sc, &n_fb, ctl + O_FB, 4) < 0 || mga_ssync(sc) < 0) return -1;
-		if (n_fb > 0 && wfs_fallback(sc, n_fb, (const int32_t*)sc->wfa_fb.p, d_prob, d_tseq, d_qseq, d_res, d_pool, pool_cap, d_pool_used) < 0) return -1;
-		ctl = (int*)sc->wfa_ctl.p; // the nested ladder may have grown the buffer
+		if (mga_d2h_s(sc, &n_fb, &ctl->fb, 4) < 0 || mga_ssync(sc) < 0) return -1;
+		if (n_fb > 0 && wfs_fallback(sc, job, n_fb, (const int32_t*)sc->wfa_fb.p) < 0) return -1;
+		ctl = (wfs_ctl_t*)sc->wfa_ctl.p; // the nested ladder may have grown the buffer
 	}
 	if (cells) {
 		unsigned long long c = 0;
 		int nb = (n + 255) / 256;
 		if (nb > 2048) nb = 2048;
-		hipLaunchKernelGGL(k_wfa_sum_cells, dim3(nb), dim3(256), 0, st, n, (const mga_wfa_res_t*)d_res, (unsigned long long*)(ctl + O_CELLS));
+		hipLaunchKernelGGL(k_wfa_sum_cells, dim3(nb), dim3(256), 0, st, n, (const mga_wfa_res_t*)job->d_res, (unsigned long long*)ctl->cells);
 		MGA_HIP_CHECK(hipGetLastError());
-		if (mga_d2h_s(sc, &c, ctl + O_CELLS, 8) < 0 || mga_ssync(sc) < 0) return -1;
+		if (mga_d2h_s(sc, &c, ctl->cells, 8) < 0 || mga_ssync(sc) < 0) return -1;
 		*cells = (int64_t)c;
 	}
 	return 0;

@@ -513,8 +513,7 @@ extern "C" int32_t mga_wfa_seg_last_step(void) { return (int32_t)__atomic_load_n
 // ---- host: driver ------------------------------------------------------------------------------
 // Runs the n problems ids[] (NULL: 0 .. n-1) of d_prob, whose lengths the caller read back into h_tl / h_ql (indexed like ids), as many side by side as fit
 // MGA_WFA_SEG_BUDGET bytes of workspace (default 32 GiB; a single problem may take more, up to what the device has free).  Results in d_res / the pool.
-extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step, const mga_wfa_prob_t *d_prob,
-							   const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used)
+extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step)
 {
 	if (n <= 0) return 0;
 	const double t0 = mga_wtime();
@@ -554,7 +553,7 @@ extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, int n, const int32_t *ids, const 
 		nt = nt < 64 ? 64 : nt > 1024 ? 1024 : nt;
 		const int kid = MGA_K_WFA0 + 8; // accounted with the widest HBM tier, like the unbounded one (k_wfa.hip)
 		mga_prof_begin(st, kid);
-		hipLaunchKernelGGL(k_wfa_seg, dim3(nb), dim3(nt), 0, st, (const wseg_job_t*)d_job, d_prob, d_tseq, d_qseq, d_res, d_out, d_pool, (long long)pool_cap, d_pool_used,
+		hipLaunchKernelGGL(k_wfa_seg, dim3(nb), dim3(nt), 0, st, (const wseg_job_t*)d_job, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool, (long long)jb->pool_cap, jb->d_pool_used,
 						   (char*)sc->wfa_seg_ws.p, g_pen);
 		mga_prof_end(st, kid);
 		MGA_HIP_CHECK(hipGetLastError());

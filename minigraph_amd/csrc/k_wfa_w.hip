@@ -994,15 +994,14 @@ static int wfw_rows(int W) { const int smax = W + 30 < WFW_SMAX ? W + 30 : WFW_S
 
 extern "C" int64_t mga_dev_wfa_win_tb_stride(int wt) { return (int64_t)wfw_rows(g_wtier[wt].W) * g_wtier[wt].W * 4; }
 
-extern "C" int mga_dev_wfa_win(mga_sctx_t *sc, const int *d_n, int n, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-							   mga_wfa_res_t *d_res, char *d_tb, int wt, int slot, mga_wfa_retry_t rt,
-							   uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int *d_err)  /* (launched on the context's own stream) */
+extern "C" int mga_dev_wfa_win(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, char *d_tb, int wt, int *d_err)
 {
+	const int n = ln->cap;
 	// MGA_WFA_FUSE_TB=1: a wavefront of the packed rungs walks its own alignment behind its forward pass instead of leaving it to k_wfa_tb.  [measured, round 6,
 	// profiles/r06z_fuse_tb.txt, 125 000 reads, isolated] k_wfa_tb 18.1 -> 11.0 ms, but the three rungs 26.5 + 20.9 + 8.5 -> 34.3 + 25.8 + 10.2 ms: at 2-4 waves per SIMD nothing
 	// hides a walk's ~60 dependent trips, and the wavefront holds its registers and LDS while it waits.  Not the default; the tests run both forms.
 	const char *e_fu = getenv("MGA_WFA_FUSE_TB");
-	const int fuse = (e_fu && *e_fu ? atoi(e_fu) : 0) && d_pool != 0 && d_pool_used != 0 && d_err != 0;
+	const int fuse = (e_fu && *e_fu ? atoi(e_fu) : 0) && job->d_pool != 0 && job->d_pool_used != 0 && d_err != 0;
 	if (n <= 0) return 0;
 	if (wt < 0 || wt >= MGA_WFW_N) { mga_set_error("wfa_win: bad tier %d", wt); return -1; }
 	const wfw_tier_t &T = g_wtier[wt];
@@ -1020,14 +1019,14 @@ extern "C" int mga_dev_wfa_win(mga_sctx_t *sc, const int *d_n, int n, const int3
 	const int cap_wg = (int)((long long)T.n_wg * grid_pct / 100) > 64 ? (int)((long long)T.n_wg * grid_pct / 100) : 64;
 	if (wgs > cap_wg) wgs = cap_wg;
 	if (wgs < 1) wgs = 1;
-	hipStream_t st = (hipStream_t)mga_wfa_stream(sc, slot);
-	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * slot);
+	hipStream_t st = (hipStream_t)(ln->stream ? ln->stream : sc->stream);
+	int *d_counter = (int*)((char*)sc->wfa_cnt.p + 64 * ln->slot);
 	const long long stride = (long long)mga_dev_wfa_win_tb_stride(wt);
 	mga_prof_begin(st, MGA_K_WFAW0 + wt);
-#define LAUNCH(GG, JJ, SEQ) hipLaunchKernelGGL((k_wfa_fw<GG, JJ, SEQ>), dim3(wgs), dim3(64), 0, st, d_n, n, d_list, d_prob, d_tseq, d_qseq, d_res, d_tb, stride, d_counter, rt)
+#define LAUNCH(GG, JJ, SEQ) hipLaunchKernelGGL((k_wfa_fw<GG, JJ, SEQ>), dim3(wgs), dim3(64), 0, st, ln->d_n, n, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, d_tb, stride, d_counter, ln->rt)
 	// (default mask 7, measured per 125 000 reads, profiles/r05n_packed_sweep.txt: 128: 45.9 -> 26.9 ms, 192: 22.8 -> 21.1 ms, 256: 12.5 -> 8.5 ms)
-#define LAUNCHQ(GG, SEQ) hipLaunchKernelGGL((k_wfa_fwq<GG, SEQ>), dim3(wgs), dim3(64), 0, st, d_n, n, d_list, d_prob, d_tseq, d_qseq, d_res, d_tb, stride, d_counter, rt)
-#define LAUNCHP(WW, SEQ) hipLaunchKernelGGL((k_wfa_fwp<WW, SEQ>), dim3(wgs), dim3(64), 0, st, d_n, n, d_list, d_prob, d_tseq, d_qseq, d_res, d_tb, stride, d_counter, rt, d_pool, (long long)pool_cap, d_pool_used, d_err, fuse)
+#define LAUNCHQ(GG, SEQ) hipLaunchKernelGGL((k_wfa_fwq<GG, SEQ>), dim3(wgs), dim3(64), 0, st, ln->d_n, n, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, d_tb, stride, d_counter, ln->rt)
+#define LAUNCHP(WW, SEQ) hipLaunchKernelGGL((k_wfa_fwp<WW, SEQ>), dim3(wgs), dim3(64), 0, st, ln->d_n, n, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, d_tb, stride, d_counter, ln->rt, job->d_pool, (long long)job->pool_cap, job->d_pool_used, d_err, fuse)
 	if (wt == 0) LAUNCH(16, 1, 128);
 	else if (wt == 1) { if (pk_mask & 16) LAUNCHQ(16, 192); else LAUNCH(32, 1, 192); }
 	else if (wt == 2) { if (pk_mask & 8) LAUNCHQ(32, 256); else LAUNCH(64, 1, 256); }
@@ -1042,14 +1041,14 @@ extern "C" int mga_dev_wfa_win(mga_sctx_t *sc, const int *d_n, int n, const int3
 	return 0;
 }
 
-extern "C" int mga_dev_wfa_traceback(mga_sctx_t *sc, void *stream, const int *d_n, int cap, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res,
-									 uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int *d_err, int wt)
+extern "C" int mga_dev_wfa_traceback(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int *d_err, int wt)
 {
-	if (cap <= 0) return 0;
+	if (ln->cap <= 0) return 0;
 	if (wt < 0 || wt >= MGA_WFW_N) { mga_set_error("wfa_traceback: bad tier %d", wt); return -1; }
-	hipStream_t st = (hipStream_t)(stream ? stream : sc->stream);
+	hipStream_t st = (hipStream_t)(ln->stream ? ln->stream : sc->stream);
 	mga_prof_begin(st, MGA_K_WFATB);
-	hipLaunchKernelGGL(k_wfa_tb, dim3((cap + 255) / 256), dim3(256), 0, st, d_n, cap, d_list, d_prob, d_tseq, d_qseq, d_res, d_pool, (long long)pool_cap, d_pool_used, d_err, g_wtier[wt].W);
+	hipLaunchKernelGGL(k_wfa_tb, dim3((ln->cap + 255) / 256), dim3(256), 0, st, ln->d_n, ln->cap, ln->d_list, job->d_prob, job->d_tseq, job->d_qseq, job->d_res, job->d_pool, (long long)job->pool_cap,
+					   job->d_pool_used, d_err, g_wtier[wt].W);
 	mga_prof_end(st, MGA_K_WFATB);
 	MGA_HIP_CHECK(hipGetLastError());
 	return 0;

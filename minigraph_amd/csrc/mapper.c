@@ -930,8 +930,6 @@ static int rq_dev_fwd_hook(void *ctx_, int n_reads, const int64_t *r_abs0, const
 	return 0;
 }
 
-static void release_token_cb(void *a) { gpu_token_t **held = (gpu_token_t**)a; if (*held) { token_release(*held); *held = 0; } }
-
 /* ---- GAF lines on the device (k_gaf.hip) ----
  * One record per line the reference's writer prints for the chunk (format.c:121-250), in print order: the printed chains of every read (in text mode exactly the chains with a
  * text-kernel chain: chain_id >= 0), or the one line of an unmapped read under MG_M_SHOW_UNMAP.  Returns the number of lines; -1: a read of the chunk has chains but no plan
@@ -983,7 +981,6 @@ typedef struct {
 	int check;          /* MGA_CHECK=1: debugging aid: invariants of what the device stages handed back (host placement) */
 	int dev_splice;     /* MGA_DEV_SPLICE=0: the gaps' targets are spliced on the host and uploaded as bytes (align.h: want_src) */
 	int dev_rmq;        /* MGA_DEV_RMQ=0: the RMQ chainer's forward passes stay on the host threads (k_rmq.hip otherwise) */
-	int early_release;  /* MGA_EARLY_RELEASE=0: the WFA token is held until the gather instead of going back once the bulk of the tier ladder is through */
 	int txt_tight;      /* MGA_TXT_TIGHT=1: a deliberately small text pool, so that a test sees the second launch */
 	int dev_gaf;        /* MGA_DEV_GAF=0: the host formats the GAF lines as in rounds 1-5 (A/B, tests) */
 	int gaf_direct;     /* MGA_GAF_DIRECT=0: a chunk's lines always go through its pieces, never straight to their place in the job's output */
@@ -995,7 +992,7 @@ static void chunk_knobs_read(chunk_knobs_t *k)
 	k->host_text = env_int("MGA_HOST_TEXT", 0), k->no_longq = env_int("MGA_NO_LONGQ", 0), k->sketch_2bit = env_int("MGA_SKETCH_2BIT", 0), k->host_rescue = env_int("MGA_HOST_RESCUE", 0);
 	k->lc_order = env_int("MGA_LC_ORDER", 1), k->dev_gchain_set = s != 0, k->dev_gchain_has = s && *s, k->dev_gchain = k->dev_gchain_has ? atoi(s) : 0;
 	k->host_gchain = env_int("MGA_HOST_GCHAIN", 0), k->dev_gchain_pct = env_int("MGA_DEV_GCHAIN_PCT", 25), k->gc_prof = env_int("MGA_GC_PROF", 0), k->dev_plan = env_int("MGA_DEV_PLAN", 1);
-	k->check = env_int("MGA_CHECK", 0), k->dev_splice = env_int("MGA_DEV_SPLICE", 1), k->dev_rmq = env_int("MGA_DEV_RMQ", 1), k->early_release = env_int("MGA_EARLY_RELEASE", 1);
+	k->check = env_int("MGA_CHECK", 0), k->dev_splice = env_int("MGA_DEV_SPLICE", 1), k->dev_rmq = env_int("MGA_DEV_RMQ", 1);
 	k->txt_tight = env_int("MGA_TXT_TIGHT", 0), k->dev_gaf = env_int("MGA_DEV_GAF", 1), k->gaf_direct = env_int("MGA_GAF_DIRECT", 1);
 }
 
@@ -1024,13 +1021,13 @@ typedef struct { /* one run of the stage sequence: a stack object of map_chunk()
 	int64_t *q_off, *h_mzoff, *h_aoff, *h_minioff; int32_t *h_nmz, *h_rep, *h_nu, *h_nb, *h_rflag;
 	/* borrowed, inside the context's pinned staging: the device-made chains' headers, the device-made gap list's first printed chain per read */
 	mga_gc_hdr_t *h_gchdr_p; int64_t *h_ploff;
-	/* state; rq_ctx and held live HERE because their addresses leave the stage that sets them: other threads use rq_ctx inside mga_batch_chain(), release_token_cb gets &held */
+	/* state; rq_ctx lives HERE because its address leaves the stage that sets it (other threads use it inside mga_batch_chain()); held because one stage acquires the token and a later one releases it */
 	const char *d_seq; double t0 /* start of the interval being timed */; mga_lchain_par_t par; rq_dev_ctx_t rq_ctx; mga_batch_t *b;
 	gpu_token_t *held; /* GPU phase token currently owned */
 } chunk_t;
 
 static void chunk_token_acquire(chunk_t *c, gpu_token_t *t) { token_acquire(t); c->held = t; }
-static void chunk_token_release(chunk_t *c) { release_token_cb(&c->held); }
+static void chunk_token_release(chunk_t *c) { if (c->held) { token_release(c->held); c->held = 0; } }
 
 /* a stage is over: its interval goes to `acc` and to the MGA_DEBUG_PIPE log */
 static void chunk_lap(chunk_t *c, const char *what, double *acc)
@@ -1497,6 +1494,7 @@ static int chunk_wfa(chunk_t *c)
 {
 	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc; const mg_mapopt_t *opt = c->opt; mga_batch_t *b = c->b; const unsigned long long *ptot = c->ptot;
 	int64_t n_prob, pool_cap;
+	mga_wfa_job_t job;
 	int i;
 	c->dp_chain = (int64_t)ptot[0], c->dp_item = (int64_t)ptot[1], c->dp_prob = (int64_t)ptot[2], c->dp_vert = (int64_t)ptot[3], c->dp_tb = (int64_t)ptot[4];
 	c->hp_prob = mga_batch_n_wfa(b), c->hp_tb = mga_batch_wfa_target_bytes(b);
@@ -1513,12 +1511,11 @@ static int chunk_wfa(chunk_t *c)
 	for (i = 0; i < b->n_threads; ++i) pool_cap += b->tp[i].wfa_q_bases;
 	CK(mga_dbuf_reserve(&P->pool, (size_t)pool_cap * 4)); CK(mga_dmemset_s(sc, P->used.p, 0, 8));
 	/* the tier ladder runs on the device (k_wfa_sched.hip); the host never walks the problems */
-	CK(mga_dev_wfa_solve(sc, (int)n_prob, (const mga_wfa_prob_t*)P->prob.p, (const char*)P->tseq.p, c->d_seq, (mga_wfa_res_t*)P->res.p,
-						 (uint32_t*)P->pool.p, pool_cap, (unsigned long long*)P->used.p, &c->cells, c->k.early_release ? release_token_cb : 0, &c->held));
+	job = (mga_wfa_job_t){ (const mga_wfa_prob_t*)P->prob.p, (const char*)P->tseq.p, c->d_seq, (mga_wfa_res_t*)P->res.p, (uint32_t*)P->pool.p, pool_cap, (unsigned long long*)P->used.p };
+	CK(mga_dev_wfa_solve(sc, &job, (int)n_prob, &c->cells));
 	/* CIGARs back in problem order: one sequential stream for the host's stitching threads, or the input of the text kernel */
 	CK(mga_dbuf_reserve(&P->ncig, (size_t)n_prob * 4 + 16)); CK(mga_dbuf_reserve(&P->cigoff, (size_t)(n_prob + 1) * 8)); CK(mga_dbuf_reserve(&P->ord, (size_t)pool_cap * 4));
-	CK(mga_dev_wfa_gather(sc, (int)n_prob, (const mga_wfa_res_t*)P->res.p, (const uint32_t*)P->pool.p, (int32_t*)P->ncig.p, (int64_t*)P->cigoff.p,
-						  (uint32_t*)P->ord.p, pool_cap, &c->n_ops));
+	CK(mga_dev_wfa_gather(sc, &job, (int)n_prob, (int32_t*)P->ncig.p, (int64_t*)P->cigoff.p, (uint32_t*)P->ord.p, pool_cap, &c->n_ops));
 	chunk_token_release(c); /* the gather kernel and what follows trail on this chunk's stream while the next chunk's kernels start */
 	return 0;
 }

@@ -39,14 +39,14 @@ void mga_dbuf_free(mga_dbuf_t *b);
 typedef struct mga_sctx_s {
 	void *stream;              /* hipStream_t */
 	mga_dbuf_t wfa_ws[10];     /* per-tier WFA workspaces (register / HBM tiers) */
-	mga_dbuf_t wfa_tbuf[8];    /* traceback regions of the windowed tiers, one buffer per pass of the ladder (k_wfa_w.hip) */
+	mga_dbuf_t wfa_tbuf[2];    /* traceback regions of the windowed tiers (k_wfa_w.hip): [0] serves every rung of a sweep; [1] only with MGA_WFA_TB_SIDE=1, where the rungs use the two in turn */
 	mga_dbuf_t wfa_cnt;        /* work-queue counters, one 64-byte line per tier */
 	mga_dbuf_t scan_tmp;       /* tile sums of mga_dev_scan_i32_to_i64 */
 	mga_dbuf_t txt_cnt, txt_off, txt_vwb, txt_el; /* text kernel scratch (k_text.hip) */
 	mga_dbuf_t wfa_list[2], wfa_key, wfa_ctl, wfa_fb; /* tier scheduler (k_wfa_sched.hip): work lists of a sweep / of the problems a sweep left open, sort keys, counters, problems for the chained fallback */
 	int wfa_own[16];           /* a sweep's initial list lengths (source of an async upload) */
-	void *tier_stream[16];      /* WFA tiers run concurrently on their own streams (long-tailed wide problems next to the small ones) */
-	void *ev_ready, *ev_done[16];
+	void *tier_stream[16];     /* side streams of a sweep of the ladder (k_wfa_sched.hip): [0] the own problems of the register / HBM rungs, [1] the walks under MGA_WFA_TB_SIDE=1; [2..15] unused */
+	void *ev_ready, *ev_done[16]; /* ev_ready: the side stream waits for the binning; ev_done[0]: the main stream waits for the side stream; [1]: a walk for its forward pass, [2], [3]: a forward pass for the walk that last read its buffer; [4..15] unused */
 	void *ev_sync;             /* event behind mga_ssync() */
 	void *stage;               /* pinned staging for small device-to-host read-backs, delivered by mga_ssync() */
 	mga_dbuf_t gc_split;       /* three-kernel form of graph chaining: counters, state list, jobs, walk vertices, state pool of the chunk in flight */
@@ -58,10 +58,6 @@ typedef struct mga_sctx_s {
 	mga_dbuf_t wfa_seg_ws, wfa_seg_job; /* low-memory WFA rung (k_wfa_seg.hip): workspaces of the problems of one launch, their descriptors and outcomes */
 } mga_sctx_t;
 static inline void mga_dev_lchain_order(mga_sctx_t *sc, const int32_t *d_order) { sc->lc_order = d_order; }
-void *mga_wfa_stream(mga_sctx_t *sc, int slot);       /* stream of WFA tier `slot` (the context's own stream unless MGA_WFA_CONCURRENT=1) */
-int mga_wfa_tiers_serial(void);
-int mga_wfa_fork(mga_sctx_t *sc);                     /* tier streams wait for everything queued on sc->stream so far */
-int mga_wfa_join(mga_sctx_t *sc);                     /* sc->stream waits for every tier stream */
 mga_sctx_t *mga_sctx_create(void);
 void mga_sctx_destroy(mga_sctx_t *sc);
 mga_sctx_t *mga_sctx_default(void);            /* lazily created, used by the stage-level API */
@@ -170,41 +166,33 @@ enum { MGA_WFA_OK = 0, MGA_WFA_PENDING = 1, MGA_WFA_RETRY_TIER = 2, MGA_WFA_POOL
 /* where a WFA kernel appends the problems that outgrew its tier (device pointers); err counts the other failures; fb_list/fb_cnt collect
  * the problems that hit the reference's 1e8-cell cap (miniwfa.c:827): they are re-done by the chained fallback (k_wfa_sched.hip) */
 typedef struct { int32_t *list; int *cnt; int *err; int32_t *fb_list; int *fb_cnt; int32_t cap; } mga_wfa_retry_t; /* (cap: room of `list`; *cnt runs past it when it overflows) */
-
-/* All tier launchers: the work list is d_list[first .. min(*d_n, cap)) -- the count is read ON THE DEVICE when the kernel starts, so that a rung can take what
+/* a JOB: the problems of one call of the ladder and where their results go (device pointers).  Sequences padded by >= 8 readable bytes; CIGARs appended to d_pool (capacity pool_cap operators, *d_pool_used bumped atomically) */
+typedef struct { const mga_wfa_prob_t *d_prob; const char *d_tseq, *d_qseq; mga_wfa_res_t *d_res; uint32_t *d_pool; int64_t pool_cap; unsigned long long *d_pool_used; } mga_wfa_job_t;
+/* a LAUNCH of one tier: the work list is d_list[first .. min(*d_n, cap)) -- the count is read ON THE DEVICE when the kernel starts, so that a rung can take what
  * the rungs below it appended in the same sweep without a host round trip; cap sizes the launch; slot picks the 64-byte work-queue counter of the launch
- * (zeroed by the caller), stream the HIP stream (NULL: the context's).
- * solves problems of the list in HBM-resident capacity tier 0..1 (4096 / 32768 diagonals); cigars are
- * appended to d_pool (capacity pool_cap ops, *d_pool_used bumped atomically); sequences must be padded by >= 8 readable bytes */
-int mga_dev_wfa(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-				mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt);
+ * (sc->wfa_cnt, zeroed by the caller), stream the HIP stream (NULL: the context's); rt: where the kernel sends what it gives up on */
+typedef struct { const int *d_n; int cap, first; const int32_t *d_list; int slot; void *stream; mga_wfa_retry_t rt; } mga_wfa_launch_t;
+
+/* HBM-resident capacity tiers 0..1 (k_wfa.hip: 4096 / 32768 diagonals); register-resident tiers (k_wfa_r.hip): tier 0-2 one wave per problem (64, 128, 192 diagonals), 3-6 two to
+ * sixteen waves (256, 512, 1024, 2048); mga_dev_wfa_tier: tier 0..8 = the register tiers, then the HBM-resident tiers */
+int mga_dev_wfa(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier);
+int mga_dev_wfa_reg(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier);
+int mga_dev_wfa_tier(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int tier);
+/* windowed tiers (k_wfa_w.hip): forward pass of tier wt (0..5) over the launch's whole list (ln->first is not used); traceback bytes go to
+ * d_tb + item * mga_dev_wfa_win_tb_stride(wt).  d_err (optional): the packed rungs (128 / 192 / 256 diagonals) may walk their own alignments (MGA_WFA_FUSE_TB=1: results
+ * final, CIGARs in the pool).  mga_dev_wfa_traceback() then turns every MGA_WFA_TB result of the SAME list (ln->d_n, cap, d_list, stream) into score + CIGAR in the pool
+ * (MGA_WFA_OK); it runs right behind the rung's forward pass, so that ONE region buffer (the largest rung's) serves the whole sweep. */
+int64_t mga_dev_wfa_win_tb_stride(int wt);
+int mga_dev_wfa_win(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, char *d_tb, int wt, int *d_err);
+#define MGA_WFA_FUSE_SLACK (3LL * 8192 * 1024) /* CIGAR pool: the abandoned tails of the blocks k_wfa_fwp's wavefronts take (three rungs, <= 8192 wavefronts, 1024 operators) */
+int mga_dev_wfa_traceback(mga_sctx_t *sc, const mga_wfa_job_t *job, const mga_wfa_launch_t *ln, int *d_err, int wt /* the rung's window tier: only results of THAT window are walked */);
+int32_t mga_wfw_window(int32_t W, int32_t tl, int32_t ql, int32_t *lo);
 /* the rung behind the last HBM tier (k_wfa_seg.hip): mwf_wfa_exact's low-memory mode, a workgroup per problem.  ids[n] (NULL: 0 .. n-1) index d_prob / d_res; h_tl / h_ql [n]
  * are those problems' lengths on the host; step 0: the host's choice (MGA_WFA_SEG_STEP, else the step of least memory).  Synchronous; fails with a message when a problem cannot be placed. */
-int mga_dev_wfa_seg(mga_sctx_t *sc, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step, const mga_wfa_prob_t *d_prob,
-					const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used);
-/* register-resident tiers (k_wfa_r.hip): tier 0-2 one wave per problem (64, 128, 192 diagonals), 3-6 two to sixteen waves (256, 512, 1024, 2048) */
-int mga_dev_wfa_reg(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-					mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt);
-/* windowed tiers (k_wfa_w.hip): forward pass of tier wt (0..5) over d_list; traceback bytes go to d_tb + item * mga_dev_wfa_win_tb_stride(wt); `slot` picks the
- * work-queue counter.  mga_dev_wfa_traceback() then turns every MGA_WFA_TB result of the SAME list into score + CIGAR in the pool (MGA_WFA_OK); it runs right
- * behind the rung's forward pass, so that ONE region buffer (the largest rung's) serves the whole sweep. */
-int64_t mga_dev_wfa_win_tb_stride(int wt);
-int mga_dev_wfa_win(mga_sctx_t *sc, const int *d_n, int cap, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-					mga_wfa_res_t *d_res, char *d_tb, int wt, int slot, mga_wfa_retry_t rt,
-					uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int *d_err /* the packed rungs (128 / 192 / 256 diagonals) walk their own alignments: results final, CIGARs in the pool */);
-#define MGA_WFA_FUSE_SLACK (3LL * 8192 * 1024) /* CIGAR pool: the abandoned tails of the blocks k_wfa_fwp's wavefronts take (three rungs, <= 8192 wavefronts, 1024 operators) */
-int mga_dev_wfa_traceback(mga_sctx_t *sc, void *stream /* NULL: the context's */, const int *d_n, int cap, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq, mga_wfa_res_t *d_res,
-						  uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int *d_err, int wt /* the rung's window tier: only results of THAT window are walked */);
-int32_t mga_wfw_window(int32_t W, int32_t tl, int32_t ql, int32_t *lo);
-/* tier 0..8: register tiers (one wave, then 2-16 waves per problem), then the HBM-resident tiers */
-int mga_wfa_first_tier(int32_t tl, int32_t ql); /* cheapest tier likely to fit, from the sequence lengths */
-int mga_dev_wfa_tier(mga_sctx_t *sc, const int *d_n, int cap, int first, int slot, void *stream, const int32_t *d_list, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-					 mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int tier, mga_wfa_retry_t rt);
-/* the whole ladder (k_wfa_sched.hip): every problem in its first tier, the ones that outgrow it one tier up, until none is left;
+int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step);
+/* the whole ladder (k_wfa_sched.hip): every problem 0 .. n-1 in its first tier, the ones that outgrow it one tier up, until none is left;
  * d_res[i] / d_pool hold the results; *cells (optional) = total wavefront cells */
-int mga_dev_wfa_solve(mga_sctx_t *sc, int n, const mga_wfa_prob_t *d_prob, const char *d_tseq, const char *d_qseq,
-					  mga_wfa_res_t *d_res, uint32_t *d_pool, int64_t pool_cap, unsigned long long *d_pool_used, int64_t *cells,
-					  void (*bulk_done)(void*), void *bulk_arg); /* bulk_done (optional): called once the tiers of <= 512 diagonals finished their first pass */
+int mga_dev_wfa_solve(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, int64_t *cells);
 
 /* the whole minimizer index of the graph on the device (k_index.hip): sketch of the n_seg segments in d_seq/d_off, sort, table, position lists;
  * fills ix->d_tab/d_pos/n_slots/bits/n_pos; the host gets the counters and the occurrence histogram (malloc'ed) */
@@ -306,9 +294,8 @@ int mga_lchain_rescue_batch(int n, const mg128_t *a, const int64_t *a_off, const
 /* targets of HOST-listed gaps spliced on the device: problem j's target = the walk d_vert[src[j].lc0 .. + n_lc] from base x0 + 1 to base x1, written at d_tseq + prob[j].t_off */
 int mga_dev_plan_target_verts(mga_sctx_t *sc, const mga_didx_t *ix, int64_t n_prob, const mga_wfa_prob_t *d_prob, const mga_plan_src_t *d_src, const uint32_t *d_vert, char *d_tseq);
 
-/* CIGARs of all problems copied into problem order: d_ncig[i] operators at d_ord + d_off[i] (d_off has n+1 entries); *h_total = d_off[n] */
-int mga_dev_wfa_gather(mga_sctx_t *sc, int n, const mga_wfa_res_t *d_res, const uint32_t *d_pool, int32_t *d_ncig, int64_t *d_off, uint32_t *d_ord,
-					   int64_t ord_cap, int64_t *h_total);
+/* CIGARs of all n problems of a solved job (its d_res / d_pool) copied into problem order: d_ncig[i] operators at d_ord + d_off[i] (d_off has n+1 entries); *h_total = d_off[n] */
+int mga_dev_wfa_gather(mga_sctx_t *sc, const mga_wfa_job_t *job, int n, int32_t *d_ncig, int64_t *d_off, uint32_t *d_ord, int64_t ord_cap, int64_t *h_total);
 
 #ifdef __cplusplus
 }

@@ -99,13 +99,12 @@ static int wfa_batch_impl(int n, const char *tseq, const int64_t *t_off, const c
 
 	std::vector<mga_wfa_res_t> res(n);
 	if (!d_pool.alloc((size_t)pool_cap * 4) || mga_dmemset_s(SC, d_used.p, 0, 8) < 0) return -1;
+	const mga_wfa_job_t job = { d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(), d_pool.as<uint32_t>(), pool_cap, (unsigned long long*)d_used.p };
 	if (seg_step >= 0) {
 		std::vector<int32_t> tl(n), ql(n);
 		for (int i = 0; i < n; ++i) tl[i] = prob[i].tl, ql[i] = prob[i].ql;
-		if (mga_dev_wfa_seg(SC, n, 0, tl.data(), ql.data(), seg_step, d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(),
-							d_pool.as<uint32_t>(), pool_cap, (unsigned long long*)d_used.p) < 0) return -1;
-	} else if (mga_dev_wfa_solve(SC, n, d_prob.as<mga_wfa_prob_t>(), d_t.as<char>(), d_q.as<char>(), d_res.as<mga_wfa_res_t>(),
-						  d_pool.as<uint32_t>(), pool_cap, (unsigned long long*)d_used.p, 0, 0, 0) < 0) return -1;
+		if (mga_dev_wfa_seg(SC, &job, n, 0, tl.data(), ql.data(), seg_step) < 0) return -1;
+	} else if (mga_dev_wfa_solve(SC, &job, n, 0) < 0) return -1;
 	if (mga_dsync() < 0 || mga_d2h(res.data(), d_res.p, (size_t)n * sizeof(mga_wfa_res_t)) < 0) return -1;
 	unsigned long long used = 0;
 	if (mga_dsync() < 0 || mga_d2h(&used, d_used.p, 8) < 0) return -1;
