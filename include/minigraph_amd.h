@@ -305,6 +305,51 @@ void mga_cov_chains_host(const gfa_t *g, int n_chain, const mga_cov_chain_t *cha
 int mga_cov_batch(const mg_idx_t *gi, int n_chain, const mga_cov_chain_t *chain, int64_t n_vert, const uint32_t *vert, int32_t min_mapq, int32_t min_blen,
 				  int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st);
 
+/* ---- ADDITIVE: bubble alleles (--call: main.c:280 + ggen.c:128-139 + asm-call.c:21-147 + gfa-bbl.c + ggsimple.c:11-101) without the reference's objects.  One BED line per
+ * bubble of the graph: sseq, ss, se, >first, >last, walk:glen:strand:qname:qs:qe ("." when no chain was attached, "*" for an empty walk).  The bubbles are found on the host
+ * (csrc/bubble.c), the candidates of every chain on the device (csrc/k_call.hip; csrc/call_core.h has the formulation), the text is written on the host. ---- */
+/* gfa_sort_ref_arc (gfa-bbl.c:11-33): the reference arc of every rank-0 vertex first in its arc list.  Call it BEFORE mg_index (main.c:280): graph chaining and the bubble
+ * finder both see the arc order.  A vertex without such an arc keeps its order (the reference asserts). */
+void mga_sort_ref_arc(gfa_t *g);
+/* gfa_bubble (gfa-bbl.c:244-372), the fields --call reads: bubble i lies on stable sequence snid between offsets ss and se and lists the oriented vertices
+ * vpool[v_off .. v_off + n_seg), source stem first, sink stem last; bubbles and vertices in the reference's order.  Release both arrays with mga_bubbles_free(). */
+typedef struct { int32_t snid, ss, se, n_seg; int64_t v_off; } mga_bubble_t;
+mga_bubble_t *mga_bubbles(const gfa_t *g, int32_t *n_bb, uint32_t **vpool);
+void mga_bubbles_free(mga_bubble_t *bb, uint32_t *vpool);
+/* the flat records of the stage (asm-call.c:47-115 over plain arrays):
+ *   per segment   bid = the last bubble that lists it (0 when none does), is_stem = first or last vertex of a bubble, is_src = first, over = more than one indexed interval
+ *                 of the segment overlaps [0, len) (asm-call.c:78)
+ *   per position  of a chain's walk: the vertex, (int32)y + 1 of the LAST and of the FIRST anchor of its linear chain, the span of the first (an lc without anchors reads
+ *                 the anchor in front of it, as asm-call.c:69 does)
+ *   per chain     its walk pos[pos_beg .. + cnt), the offset of that walk in the read's lc[] (st / en are reported as lc indices), the sequence t it belongs to and its
+ *                 ordinal in (t, i) order over the whole job
+ *   per sequence  its indexed query intervals qintv[q_off[t] .. q_off[t + 1]), in any order
+ * out: one record per surviving candidate, one per folded-inversion warning (type 1 or 2; v = the vertex at st); key = ord << 32 | j orders both */
+typedef struct { int32_t bid; uint8_t is_stem, is_src, over, pad; } mga_call_seg_t;
+typedef struct { uint32_t v; int32_t yl1, yf1, span; } mga_call_pos_t;
+typedef struct { int64_t pos_beg; int32_t cnt, lc_off, t, ord; } mga_call_chain_t;
+typedef struct { int32_t st, en; } mga_call_intv_t;
+typedef struct { uint64_t key; int32_t bid, st, en, strand, qs, qe, glen, t; } mga_call_cand_t;
+typedef struct { uint64_t key; int32_t type, t, qs, qe; uint32_t v; int32_t pad; } mga_call_warn_t;
+/* the stage through k_call.hip (host pointers in and out): win[n_bb] = per bubble the surviving candidate of largest key (key == 0: none), *warn (malloc'ed, release with
+ * mga_free()) = the warnings sorted by key.  mga_call_batch_host: the same through the host instantiation of call_core.h, no device needed.  Both return 0, or -1 when a
+ * record points outside its array (nothing is followed). */
+int mga_call_batch(int n_chain, const mga_call_chain_t *chain, int64_t n_pos, const mga_call_pos_t *pos, uint32_t n_seg, const mga_call_seg_t *seg, const int32_t *seg_len,
+				   int n_seq, const int64_t *q_off, const mga_call_intv_t *qintv, int32_t n_bb, mga_call_cand_t *win, mga_call_warn_t **warn, int64_t *n_warn);
+int mga_call_batch_host(int n_chain, const mga_call_chain_t *chain, int64_t n_pos, const mga_call_pos_t *pos, uint32_t n_seg, const mga_call_seg_t *seg, const int32_t *seg_len,
+						int n_seq, const int64_t *q_off, const mga_call_intv_t *qintv, int32_t n_bb, mga_call_cand_t *win, mga_call_warn_t **warn, int64_t *n_warn);
+/* mg_call_asm (asm-call.c:21-147) with its arguments (qnames[t] in place of seq[t].name): the BED is APPENDED to *out, the two warning texts go to stderr in the reference's
+ * order.  When no chain is indexed (mg_gc_index returns 0, ggsimple.c:33-36) nothing is written.  A NULL gcs[t] is a sequence without chains.  mga_call_asm runs the
+ * candidates on the device and fails (-1, mga_last_error()) without one; mga_call_asm_host is the same routine on the calling thread and needs no device. */
+int mga_call_asm(const mg_idx_t *gi, int32_t n_seq, const char *const *qnames, mg_gchains_t *const *gcs, int32_t min_mapq, int32_t min_blen, kstring_t *out);
+int mga_call_asm_host(const gfa_t *g, int32_t n_seq, const char *const *qnames, mg_gchains_t *const *gcs, int32_t min_mapq, int32_t min_blen, kstring_t *out);
+/* mg_ggen_call (ggen.c:128-139) behind main.c:280: sort the reference arcs, index, map every sequence of fn through mg_map_batch(), call, print to fp.  Base alignment runs
+ * when opt0 has MG_M_CIGAR (the intervals read gc->p->ss / ee); no GAF is made.  MG_M_FRAG_MODE is refused (-1).  mga_call_times: wall seconds of the phases of the last
+ * mga_call_files() / mga_call_asm*() on this thread's process: [0] sort + index, [1] read + map, [2] bubbles, [3] intervals + flatten, [4] candidates (kernel with its
+ * copies, or the host loop), [5] text. */
+int mga_call_files(gfa_t *g, const char *fn, const mg_idxopt_t *ipt, const mg_mapopt_t *opt0, const mg_ggopt_t *gpt, int n_threads, FILE *fp);
+void mga_call_times(double t[6]);
+
 /* a read set kept resident in HBM across calls (repeated passes over one batch, as the benchmark does) */
 typedef struct mga_reads_s mga_reads_t;
 mga_reads_t *mga_reads_load(const char *fn, int64_t max_reads);   /* FASTA/FASTQ(.gz) -> host copy + HBM copy; NULL on error */

@@ -625,6 +625,131 @@ def cov_batch(graph, chains, vert, min_mapq, min_blen):
     return sb, lc, _cov_stats(st)
 
 
+bubble_dtype = np.dtype([("snid", "<i4"), ("ss", "<i4"), ("se", "<i4"), ("n_seg", "<i4"), ("v_off", "<i8")])   # mga_bubble_t
+call_seg_dtype = np.dtype([("bid", "<i4"), ("is_stem", "u1"), ("is_src", "u1"), ("over", "u1"), ("pad", "u1")])   # mga_call_seg_t
+call_pos_dtype = np.dtype([("v", "<u4"), ("yl1", "<i4"), ("yf1", "<i4"), ("span", "<i4")])   # mga_call_pos_t
+call_chain_dtype = np.dtype([("pos_beg", "<i8"), ("cnt", "<i4"), ("lc_off", "<i4"), ("t", "<i4"), ("ord", "<i4")])   # mga_call_chain_t
+call_intv_dtype = np.dtype([("st", "<i4"), ("en", "<i4")])   # mga_call_intv_t
+call_cand_dtype = np.dtype([("key", "<u8"), ("bid", "<i4"), ("st", "<i4"), ("en", "<i4"), ("strand", "<i4"), ("qs", "<i4"), ("qe", "<i4"), ("glen", "<i4"), ("t", "<i4")])   # mga_call_cand_t
+call_warn_dtype = np.dtype([("key", "<u8"), ("type", "<i4"), ("t", "<i4"), ("qs", "<i4"), ("qe", "<i4"), ("v", "<u4"), ("pad", "<i4")])   # mga_call_warn_t
+
+
+def sort_ref_arc(g):
+    """mga_sort_ref_arc on a gfa_t* (before the index is built)"""
+    L = load()
+    L.mga_sort_ref_arc.argtypes, L.mga_sort_ref_arc.restype = [C.c_void_p], None
+    L.mga_sort_ref_arc(g)
+
+
+def bubbles(g):
+    """mga_bubbles on a gfa_t* (or a Graph) -> (records of bubble_dtype, uint32 vertex pool); bubble i lists pool[v_off : v_off + n_seg]"""
+    L = load()
+    g = getattr(g, "g", g)
+    L.mga_bubbles.argtypes, L.mga_bubbles.restype = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)], C.c_void_p
+    L.mga_bubbles_free.argtypes, L.mga_bubbles_free.restype = [C.c_void_p, C.c_void_p], None
+    n, pool = C.c_int32(0), C.c_void_p()
+    bb = L.mga_bubbles(g, C.byref(n), C.byref(pool))
+    rec = np.empty(n.value, dtype=bubble_dtype)
+    if n.value:
+        C.memmove(rec.ctypes.data, bb, rec.nbytes)
+    n_v = int((rec["v_off"] + rec["n_seg"]).max()) if n.value else 0
+    v = np.empty(n_v, dtype=np.uint32)
+    if n_v:
+        C.memmove(v.ctypes.data, pool.value, v.nbytes)
+    L.mga_bubbles_free(bb, pool)
+    return rec, v
+
+
+def _call_batch(fn, chains, pos, seg, seg_len, q_off, qintv, n_bb):
+    L = load()
+    ch, ps = np.ascontiguousarray(chains, dtype=call_chain_dtype), np.ascontiguousarray(pos, dtype=call_pos_dtype)
+    sg, sl = np.ascontiguousarray(seg, dtype=call_seg_dtype), np.ascontiguousarray(seg_len, dtype=np.int32)
+    qo, qi = np.ascontiguousarray(q_off, dtype=np.int64), np.ascontiguousarray(qintv, dtype=call_intv_dtype)
+    assert len(sg) == len(sl) and len(qo) >= 1 and int(qo[-1]) <= len(qi)
+    win = np.zeros(max(n_bb, 1), dtype=call_cand_dtype)
+    warn, n_warn = C.c_void_p(), C.c_int64(0)
+    f = getattr(L, fn)
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    _check(f(len(ch), ch.ctypes.data, len(ps), ps.ctypes.data, len(sg), sg.ctypes.data, sl.ctypes.data, len(qo) - 1, qo.ctypes.data, qi.ctypes.data, n_bb, win.ctypes.data,
+             C.byref(warn), C.byref(n_warn)), fn)
+    return win[:n_bb], _take(warn, n_warn.value, call_warn_dtype)
+
+
+def call_batch(chains, pos, seg, seg_len, q_off, qintv, n_bb):
+    """the candidates of --call for flat records through k_call.hip -> (winner per bubble, key 0 = none; warnings in key order)"""
+    return _call_batch("mga_call_batch", chains, pos, seg, seg_len, q_off, qintv, n_bb)
+
+
+def call_chains_host(chains, pos, seg, seg_len, q_off, qintv, n_bb):
+    """the same records through the host instantiation of call_core.h (no GPU)"""
+    return _call_batch("mga_call_batch_host", chains, pos, seg, seg_len, q_off, qintv, n_bb)
+
+
+def _call_asm(fn, handle, names, gcs, min_mapq, min_blen):
+    L = load()
+    n = len(names)
+    f = getattr(L, fn)
+    f.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.POINTER(kstring_t)]
+    ks = kstring_t(0, 0, None)
+    rc = f(handle, n, (C.c_char_p * n)(*names), (C.c_void_p * n)(*gcs), min_mapq, min_blen, C.byref(ks))
+    out = C.string_at(ks.s, ks.l) if ks.l else b""
+    L.mga_free(ks.s)
+    _check(rc, fn)
+    return out
+
+
+def call_asm(graph, names, gcs, min_mapq=5, min_blen=100000):
+    """mga_call_asm: the BED of `--call` from the mg_gchains_t* of every sequence of one file (input order), candidates on the device; graph: a Graph"""
+    return _call_asm("mga_call_asm", graph.gi, names, gcs, min_mapq, min_blen)
+
+
+def call_asm_host(g, names, gcs, min_mapq=5, min_blen=100000):
+    """mga_call_asm_host: the same on the calling thread, no GPU; g: a gfa_t*"""
+    return _call_asm("mga_call_asm_host", g, names, gcs, min_mapq, min_blen)
+
+
+def call_times():
+    """wall seconds of the phases of the last call_files() / call_asm*(): sort + index, read + map, bubbles, intervals + flatten, candidates, text"""
+    t = (C.c_double * 6)()
+    load().mga_call_times(t)
+    return dict(zip(("index", "map", "bubbles", "flatten", "candidates", "text"), t))
+
+
+def call_files(graph_path, query_path, preset="asm", cigar=True, n_threads=8, verbose=1, min_mapq=None, min_map_len=None):
+    """gfa_read + mga_call_files: the whole `minigraph -cx asm --call graph query` job through the C ABI -> BED bytes"""
+    import tempfile
+    L = load()
+    io, mo, go = idxopt_t(), mapopt_t(), ggopt_t()
+    L.mg_opt_set(None, C.byref(io), C.byref(mo), C.byref(go))
+    if L.mg_opt_set(preset.encode(), C.byref(io), C.byref(mo), C.byref(go)) != 0:
+        raise ValueError("unknown preset %r" % preset)
+    if cigar:
+        mo.flag |= MG_M_CIGAR
+    if min_mapq is not None:
+        go.min_mapq = min_mapq
+    if min_map_len is not None:
+        go.min_map_len = min_map_len
+    C.c_int.in_dll(L, "mg_verbose").value = verbose
+    g = L.gfa_read(graph_path.encode())
+    if not g:
+        raise RuntimeError("gfa_read(%s) failed" % graph_path)
+    libc = C.CDLL(None)
+    libc.fopen.restype, libc.fopen.argtypes, libc.fclose.argtypes = C.c_void_p, [C.c_char_p, C.c_char_p], [C.c_void_p]
+    L.mga_call_files.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(idxopt_t), C.POINTER(mapopt_t), C.POINTER(ggopt_t), C.c_int, C.c_void_p]
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "call.bed")
+        fp = libc.fopen(path.encode(), b"wb")
+        if not fp:
+            L.gfa_destroy(g)
+            raise OSError("cannot open %s" % path)
+        rc = L.mga_call_files(g, query_path.encode(), C.byref(io), C.byref(mo), C.byref(go), n_threads, C.c_void_p(fp))
+        libc.fclose(C.c_void_p(fp))
+        L.gfa_destroy(g)
+        _check(rc, "mga_call_files")
+        return open(path, "rb").read()
+
+
 def get_stats(graph, reset=False):
     st = stats_t()
     load().mga_get_stats(graph.gi, C.byref(st), 1 if reset else 0)

@@ -164,6 +164,28 @@ void mga_reads_free(mga_reads_t *rd)
 	free(rd);
 }
 
+/* every record of a file as the mapper reads them (upper case, U -> T), on the host alone: what ggen_map (ggen.c:46-58) holds before it maps; the caller frees each string and the arrays */
+int mga_reads_read_host(const char *fn, int *n, int **qlens, char ***seqs, char ***names)
+{
+	rd_t r;
+	int last = 0, m = 0;
+	str_t name = {0, 0, 0}, seq = {0, 0, 0};
+	*n = 0, *qlens = 0, *seqs = 0, *names = 0;
+	memset(&r, 0, sizeof r);
+	r.fp = gzopen(fn, "r");
+	if (r.fp == 0) { mga_set_error("cannot open '%s'", fn); return -1; }
+	r.buf = (char*)malloc(RD_BUF);
+	while (read_record(&r, &last, &name, &seq) == 0) {
+		if (*n == m) { m = m ? m << 1 : 64; *qlens = MGA_REALLOC(int, *qlens, m); *seqs = MGA_REALLOC(char*, *seqs, m); *names = MGA_REALLOC(char*, *names, m); }
+		seq_normalize(seq.s, seq.l);
+		(*seqs)[*n] = (char*)malloc(seq.l + 1); memcpy((*seqs)[*n], seq.s, seq.l + 1);
+		(*names)[*n] = (char*)malloc(name.l + 1); memcpy((*names)[*n], name.s, name.l + 1);
+		(*qlens)[(*n)++] = (int)seq.l;
+	}
+	free(name.s); free(seq.s); free(r.buf); gzclose(r.fp);
+	return 0;
+}
+
 int mga_reads_count(const mga_reads_t *rd) { return rd->n; }
 int64_t mga_reads_bases(const mga_reads_t *rd) { return rd->n_bases; }
 

@@ -237,6 +237,17 @@ int mga_dev_gaf(mga_sctx_t *sc, const mga_didx_t *ix, int n_lines, const mga_gaf
 int mga_dev_cov(mga_sctx_t *sc, const mga_didx_t *ix, int n_chain, const mga_cov_chain_t *d_chain, const uint32_t *d_vert, int64_t n_vert,
 				int32_t min_mapq, int32_t min_blen, int64_t *d_seg_bases, int64_t *d_link_cnt, int64_t *d_cnt);
 
+/* ---- bubble alleles on the device (k_call.hip, call_core.h): mg_call_asm's scan, asm-call.c:47-115, over flat records ----
+ * d_best[n_bb] (largest surviving key per bubble) and d_cnt[2] (survivors, warnings written) are zeroed by the caller */
+int mga_dev_call(mga_sctx_t *sc, int n_chain, const mga_call_chain_t *d_chain, int64_t n_pos, const mga_call_pos_t *d_pos, uint32_t n_seg, const mga_call_seg_t *d_seg,
+				 const int32_t *d_seg_len, int n_seq, const int64_t *d_q_off, const mga_call_intv_t *d_qintv, int32_t n_bb, uint64_t *d_best, mga_call_cand_t *d_cand,
+				 int64_t cap_cand, mga_call_warn_t *d_warn, int64_t cap_warn, uint64_t *d_cnt);
+/* call.c: what both batch entries refuse, the winner per bubble (best != NULL: the record must carry the device's maximum), the warnings in key order */
+int mga_call_batch_check(int n_chain, const mga_call_chain_t *chain, int64_t n_pos, const mga_call_pos_t *pos, uint32_t n_seg, const mga_call_seg_t *seg,
+						 int n_seq, const int64_t *q_off, int32_t n_bb);
+int mga_call_pick(int32_t n_bb, int64_t n_cand, const mga_call_cand_t *cand, const uint64_t *best, mga_call_cand_t *win);
+void mga_call_sort_warn(int64_t n, mga_call_warn_t *w);
+
 /* ---- graph chaining on the device (k_gchain.hip, gc_core.h): from the chains of k_lchain to filtered graph chains ---- */
 typedef struct { int32_t n_gc, n_lc, n_a, status; int64_t gc_off, lc_off, a_off; } mga_gc_hdr_t; /* per read: records at gc_pool + gc_off, lc_pool + lc_off, anchors at a_pool + a_off */
 #define MGA_GC_E_POOL 3   /* status: the chunk's record pools were too small: grow and re-run the listed reads */

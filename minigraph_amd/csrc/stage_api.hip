@@ -332,3 +332,38 @@ extern "C" int mga_cov_batch(const mg_idx_t *gi, int n_chain, const mga_cov_chai
 	if (st) st->chains_counted += cnt[MGA_COV_CHAINS], st->links_counted += cnt[MGA_COV_LINKS], st->links_skipped += cnt[MGA_COV_SKIPPED];
 	return 0;
 }
+
+// mg_call_asm's scan (asm-call.c:47-115) for flat records through k_call.hip: win[n_bb] = the surviving candidate of largest key per bubble, *warn = the warnings by key
+extern "C" int mga_call_batch(int n_chain, const mga_call_chain_t *chain, int64_t n_pos, const mga_call_pos_t *pos, uint32_t n_seg, const mga_call_seg_t *seg, const int32_t *seg_len,
+							  int n_seq, const int64_t *q_off, const mga_call_intv_t *qintv, int32_t n_bb, mga_call_cand_t *win, mga_call_warn_t **warn, int64_t *n_warn)
+{
+	*warn = 0, *n_warn = 0;
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	if (mga_call_batch_check(n_chain, chain, n_pos, pos, n_seg, seg, n_seq, q_off, n_bb) < 0) return -1; // the kernel does not follow such a record either; here the caller hears about it
+	const int64_t n_q = n_seq > 0 ? q_off[n_seq] : 0;
+	const size_t cap = (size_t)n_pos + 1;
+	dptr d_chain, d_pos, d_seg, d_len, d_qoff, d_q, d_best, d_cand, d_warn, d_cnt;
+	if (!d_chain.alloc((size_t)(n_chain + 1) * sizeof *chain) || !d_pos.alloc(cap * sizeof *pos) || !d_seg.alloc((size_t)(n_seg + 1) * sizeof *seg) || !d_len.alloc((size_t)(n_seg + 1) * 4) ||
+		!d_qoff.alloc((size_t)(n_seq + 2) * 8) || !d_q.alloc((size_t)(n_q + 1) * sizeof *qintv) || !d_best.alloc((size_t)(n_bb + 1) * 8) || !d_cand.alloc(cap * sizeof(mga_call_cand_t)) ||
+		!d_warn.alloc(cap * sizeof(mga_call_warn_t)) || !d_cnt.alloc(64)) return -1;
+	if (mga_dmemset_s(SC, d_best.p, 0, (size_t)(n_bb + 1) * 8) < 0 || mga_dmemset_s(SC, d_cnt.p, 0, 64) < 0) return -1;
+	if ((n_chain > 0 && mga_h2d(d_chain.p, chain, (size_t)n_chain * sizeof *chain) < 0) || (n_pos > 0 && mga_h2d(d_pos.p, pos, (size_t)n_pos * sizeof *pos) < 0) ||
+		(n_seg > 0 && (mga_h2d(d_seg.p, seg, (size_t)n_seg * sizeof *seg) < 0 || mga_h2d(d_len.p, seg_len, (size_t)n_seg * 4) < 0)) ||
+		(n_seq > 0 && mga_h2d(d_qoff.p, q_off, (size_t)(n_seq + 1) * 8) < 0) || (n_q > 0 && mga_h2d(d_q.p, qintv, (size_t)n_q * sizeof *qintv) < 0)) return -1;
+	if (mga_dev_call(SC, n_chain, d_chain.as<mga_call_chain_t>(), n_pos, d_pos.as<mga_call_pos_t>(), n_seg, d_seg.as<mga_call_seg_t>(), d_len.as<int32_t>(), n_seq, d_qoff.as<int64_t>(),
+					 d_q.as<mga_call_intv_t>(), n_bb, d_best.as<uint64_t>(), d_cand.as<mga_call_cand_t>(), (int64_t)n_pos, d_warn.as<mga_call_warn_t>(), (int64_t)n_pos, d_cnt.as<uint64_t>()) < 0) return -1;
+	uint64_t cnt[8];
+	if (mga_ssync(SC) < 0 || mga_d2h(cnt, d_cnt.p, 64) < 0) return -1;
+	if ((int64_t)cnt[0] > n_pos || (int64_t)cnt[1] > n_pos) { mga_set_error("call: the kernel reports more candidates than walk positions"); return -1; }
+	std::vector<uint64_t> best((size_t)n_bb + 1);
+	std::vector<mga_call_cand_t> hc((size_t)cnt[0] + 1);
+	mga_call_warn_t *hw = (mga_call_warn_t*)malloc(((size_t)cnt[1] + 1) * sizeof(mga_call_warn_t));
+	if ((n_bb > 0 && mga_d2h(best.data(), d_best.p, (size_t)n_bb * 8) < 0) || (cnt[0] > 0 && mga_d2h(hc.data(), d_cand.p, (size_t)cnt[0] * sizeof(mga_call_cand_t)) < 0) ||
+		(cnt[1] > 0 && mga_d2h(hw, d_warn.p, (size_t)cnt[1] * sizeof(mga_call_warn_t)) < 0)) { free(hw); return -1; }
+	if (mga_call_pick(n_bb, (int64_t)cnt[0], hc.data(), best.data(), win) < 0) { free(hw); mga_set_error("call: a bubble's largest key has no candidate record"); return -1; }
+	mga_call_sort_warn((int64_t)cnt[1], hw);
+	*warn = hw, *n_warn = (int64_t)cnt[1];
+	return 0;
+}

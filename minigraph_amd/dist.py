@@ -156,6 +156,41 @@ def ggen_map_sharded(graph, qlens, seqs, names, n_threads=8, dst=0, device="cpu"
     return None if parts is None else ggen_assemble(parts, n)
 
 
+def call_from_parts(graph, parts, names, min_mapq=None, min_blen=None):
+    """rank `dst`: the packed chains of every rank (rank order) -> the file's objects in input order (mga_ggen_assemble) -> the BED of `--call` (mga_call_asm: candidates on
+    this rank's device).  The graph's reference arcs must have been sorted (sort_ref_arc) before its index was built, on every rank."""
+    import ctypes as C
+    from . import load, call_asm
+    L = load()
+    L.mg_gchain_free.argtypes, L.mg_gchain_free.restype = [C.c_void_p], None
+    gcs = ggen_assemble(parts, len(names))
+    try:
+        return call_asm(graph, names, gcs, graph.go.min_mapq if min_mapq is None else min_mapq, graph.go.min_map_len if min_blen is None else min_blen)
+    finally:
+        for p in gcs:
+            if p:
+                L.mg_gchain_free(p)
+
+
+def call_sharded(graph, qlens, seqs, names, n_threads=8, dst=0, device="cpu", min_mapq=None, min_blen=None):
+    """`minigraph -cx asm --call` (ggen.c:128-139) over the ranks of a node: ggen_map_sharded's shard -> pack -> gather -> assemble route, ended on rank `dst` by
+    mga_call_asm.  Returns the BED bytes on `dst`, None elsewhere."""
+    import ctypes as C
+    from . import load
+    L = load()
+    L.mg_gchain_free.argtypes, L.mg_gchain_free.restype = [C.c_void_p], None
+    gcs = ggen_map_sharded(graph, qlens, seqs, names, n_threads=n_threads, dst=dst, device=device)
+    if gcs is None:
+        return None
+    from . import call_asm
+    try:
+        return call_asm(graph, names, gcs, graph.go.min_mapq if min_mapq is None else min_mapq, graph.go.min_map_len if min_blen is None else min_blen)
+    finally:
+        for p in gcs:
+            if p:
+                L.mg_gchain_free(p)
+
+
 def assemble_segments(parts, seg_lens):
     """rank-order concatenation PER SEGMENT: parts[r] = the bytes rank r produced (its segments back to back), seg_lens[r][s] = how many
     of them belong to output segment s (a memory-mapped FASTA file is one segment cut by byte range; any other input has one segment per
