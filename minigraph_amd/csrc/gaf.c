@@ -9,7 +9,7 @@
 #include "mga_host.h"
 
 /* A kstring_t whose capacity says MGA_KS_WINDOW is a WINDOW into somebody else's buffer (round 5: a chunk's GAF lines written straight to their place in the job's output,
- * mapper.c): it is never reallocated and never NUL-terminated -- the byte behind a piece belongs to the next piece, which another thread may be writing. */
+ * batch.c: gaf_worker, mode 2): it is never reallocated and never NUL-terminated -- the byte behind a piece belongs to the next piece, which another thread may be writing. */
 #define KS_TERM(s) do { if ((s)->m != MGA_KS_WINDOW) (s)->s[(s)->l] = 0; } while (0)
 static __thread size_t ks_win_limit = 0; /* bytes the calling thread's current window holds (mga_gaf_window_limit): a write past it lands in the next thread's piece */
 void mga_gaf_window_limit(size_t bytes) { ks_win_limit = bytes; }

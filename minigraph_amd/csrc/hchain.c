@@ -84,7 +84,7 @@ mg128_t *mga_compact_a(int32_t n_u, uint64_t *u, int32_t n_v, const int32_t *v, 
  * k_lchain gives a read one wavefront: ~10 k cycles per anchor are hidden by the other reads' wavefronts when a chunk holds thousands of 10 kb reads, but a 5 Mbp read
  * is 3 x 10^5 dependent anchor steps on ONE wavefront ([measured] 1.4 s, round 1-3: slower than the whole reference job).  A host core takes the same steps from its
  * caches in ~0.1 s, and reads of that length are few, so they are placed here -- like the RMQ chainer of -x asm -- while sketch, seeds, WFA and text stay on the device
- * (the long-query path of mapper.c).  Fills f, p, v (t: zeroed by the caller); the caller backtracks with mga_chain_backtrack / mga_compact_a. */
+ * (the long-query path: rqphase.c, rq_fwd_worker).  Fills f, p, v (t: zeroed by the caller); the caller backtracks with mga_chain_backtrack / mga_compact_a. */
 typedef struct { int32_t dist_x, dist_y, bw; float pen_gap, pen_skip; } lcdp_par_t;
 
 static inline int lcdp_pair(const mg128_t *ai, const mg128_t *aj, const lcdp_par_t *P, int32_t *sc_) /* comput_sc (lchain.c:114-139) for one segment: 0 when aj cannot precede ai */

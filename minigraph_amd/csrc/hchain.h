@@ -1,4 +1,4 @@
-/* hchain.h -- host-side chaining stages shared by rmq.c, gchain.c and mapper.c */
+/* hchain.h -- host-side chaining stages shared by rmq.c, gchain.c, batch.c and rqphase.c */
 #ifndef MGA_HCHAIN_H
 #define MGA_HCHAIN_H
 #include "mga_host.h"

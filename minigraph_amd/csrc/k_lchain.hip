@@ -999,7 +999,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
 	if (threadIdx.x < 32) L.prof[threadIdx.x] = 0;
 	const int lane = threadIdx.x;
 	if ((int)blockIdx.x >= n_reads) return;
-	const int r = order ? __builtin_amdgcn_readfirstlane(order[blockIdx.x]) : (int)blockIdx.x; // workgroups are dispatched in index order: the reads with the most anchors first (mapper.c)
+	const int r = order ? __builtin_amdgcn_readfirstlane(order[blockIdx.x]) : (int)blockIdx.x; // workgroups are dispatched in index order: the reads with the most anchors first (chunk.c: chunk_lchain)
 	if (lane == 0 && d_flag) d_flag[r] = 0;
 	lc_read_t X;
 	lc_read_setup(r, a_all, a_off, P, R, q_off, u_all, b_all, ws_i32, ws_z, &X);

@@ -1,5 +1,5 @@
 /*
- * mapfiles.c -- file-level driver: mg_map_files() (reference gmap.c:163-211) on top of the chunk pipeline (mapper.c: mga_stream_*).
+ * mapfiles.c -- file-level driver: mg_map_files() (reference gmap.c:163-211) on top of the chunk pipeline (stream.c: mga_stream_*).
  * Reads FASTA/FASTQ (plain or gzip), upper-cases and converts U->T like the reference (gmap.c:81, bseq.c:50-58), maps
  * mini-batches of opt->mini_batch_size bases and writes GAF in input order.  Two readers with kseq's record semantics
  * (bseq.c:61-98 via kseq.h): a sequential one for anything gzopen() can read, and a parallel one for plain FASTA files
@@ -204,7 +204,7 @@ int mga_map_reads(const mg_idx_t *gi, const mga_reads_t *rd, const mg_mapopt_t *
 
 /* ---- mg_map_files (gmap.c:163-211): read -> map -> write as overlapped stages, like the reference's kt_pipeline (gmap.c:70-141).
  * A reader thread parses mini-batches of opt->mini_batch_size bases; the calling thread submits them to ONE chunk pipeline that
- * lives for the whole job (mapper.c: mga_stream_*; chunks of consecutive mini-batches follow each other without a drain); a
+ * lives for the whole job (stream.c: mga_stream_*; chunks of consecutive mini-batches follow each other without a drain); a
  * collector thread takes the finished batches in input order and hands their GAF text to the writer thread. ---- */
 #include <pthread.h>
 #include <sys/mman.h>
@@ -296,12 +296,9 @@ static const char *fa_next_rec(const char *p, const char *end) /* first '>' at t
 	return end;
 }
 
-/* MGA_DEBUG_PIPE accounting (mapper.c) */
-void mga_cpu_note(int which, int64_t ns);
-int64_t mga_cpu_now(void);
 typedef struct { const char **cut; fa_list_t *list; } fa_scan_t;
 static void fa_scan_worker1(void *data, int64_t j, int tid);
-static void fa_scan_worker(void *data, int64_t j, int tid) { int64_t t0 = mga_cpu_now(); fa_scan_worker1(data, j, tid); if (t0) mga_cpu_note(15, mga_cpu_now() - t0); }
+static void fa_scan_worker(void *data, int64_t j, int tid) { int64_t t0 = mga_cpu_now(); fa_scan_worker1(data, j, tid); if (t0) mga_cpu_note(C_FASCAN, mga_cpu_now() - t0); }
 static void fa_scan_worker1(void *data, int64_t j, int tid)
 {
 	fa_scan_t *S = (fa_scan_t*)data;
@@ -371,7 +368,7 @@ static int fa_scan_window(fa_fast_t *F, int64_t want)
 
 typedef struct { const fa_rec_t *rec; fbatch_t *b; } fa_fill_t;
 static void fa_fill_worker1(void *data, int64_t i, int tid);
-static void fa_fill_worker(void *data, int64_t i, int tid) { int64_t t0 = mga_cpu_now(); fa_fill_worker1(data, i, tid); if (t0) mga_cpu_note(15, mga_cpu_now() - t0); }
+static void fa_fill_worker(void *data, int64_t i, int tid) { int64_t t0 = mga_cpu_now(); fa_fill_worker1(data, i, tid); if (t0) mga_cpu_note(C_FASCAN, mga_cpu_now() - t0); }
 static void fa_fill_worker1(void *data, int64_t i, int tid)
 {
 	fa_fill_t *f = (fa_fill_t*)data;
@@ -459,7 +456,7 @@ static int seq_batch(rd_t *r, int *last, str_t *name, int64_t batch_bases, fbatc
 }
 
 static void *reader_main1(void *a);
-static void *reader_main(void *a) { int64_t t0 = mga_cpu_now(); void *r = reader_main1(a); if (t0) mga_cpu_note(14, mga_cpu_now() - t0); return r; }
+static void *reader_main(void *a) { int64_t t0 = mga_cpu_now(); void *r = reader_main1(a); if (t0) mga_cpu_note(C_READER, mga_cpu_now() - t0); return r; }
 static void *reader_main1(void *a)
 {
 	reader_t *R = (reader_t*)a;
@@ -658,7 +655,7 @@ static void *writer_main(void *a)
 				memcpy(s->mem + s->mem_len, w->buf, (size_t)w->len); s->mem_len += w->len;
 			}
 		}
-		if (t0_) mga_cpu_note(16, mga_cpu_now() - t0_);
+		if (t0_) mga_cpu_note(C_WRITER, mga_cpu_now() - t0_);
 		pthread_mutex_lock(W->pool_m); W->pool[(*W->n_pool)++] = w; pthread_mutex_unlock(W->pool_m); /* the buffer goes back to the submitter */
 	}
 	return 0;

@@ -1,4 +1,4 @@
-/* mapper.h -- host-side batch object shared by mapper.c and the stage tests */
+/* mapper.h -- the host-side batch object (batch.c) as the chunk pipeline and the stage tests see it */
 #ifndef MGA_MAPPER_H
 #define MGA_MAPPER_H
 #include "mga_host.h"
@@ -22,4 +22,7 @@ int mga_batch_finish_ordered(mga_batch_t *b, const int32_t *ncig, const int64_t 
 mg_gchains_t **mga_batch_take_results(mga_batch_t *b);
 void mga_batch_stats(const mga_batch_t *b, mga_stats_t *st);
 void mga_batch_destroy(mga_batch_t *b);
+/* the cache of GAF piece buffers (batch.c): a chunk's pieces are filled from it, whoever has copied a piece out hands its buffer back */
+MGA_LOCAL char *strbuf_get(size_t want, size_t *cap);
+MGA_LOCAL void strbuf_put(char *p, size_t m);
 #endif

@@ -29,6 +29,11 @@ double mga_wtime(void);
 int  mga_host_pin(void *p, size_t bytes);      /* hipHostRegister with a registry: mga_free() and every realloc / free inside the library unregister first */
 void mga_host_unpin(void *p);
 
+/* ---- MGA_DEBUG_PIPE: per-stage host CPU time (thread clocks), summed over worker threads (stream.c) ---- */
+enum { C_LCCOPY, C_LCRESCUE, C_LCPREP, C_GCDP, C_GCGEN, C_GCPOST, C_PLAN, C_APPLY, C_DS, C_GAF, C_EXPORT, C_PIPE, C_SYNC, C_COMMIT, C_READER, C_FASCAN, C_WRITER, C_N };
+void mga_cpu_note(int which, int64_t ns);      /* adds ns to stage `which`; nothing when the accounting is off */
+int64_t mga_cpu_now(void);                     /* this thread's CPU clock; 0 when the accounting is off */
+
 /* grow-only device buffer */
 typedef struct { void *p; size_t cap; } mga_dbuf_t;
 int  mga_dbuf_reserve(mga_dbuf_t *b, size_t bytes); /* contents are NOT preserved on growth */

@@ -299,7 +299,7 @@ void mga_rq_tie_stats(int64_t *out, int reset) { int k; for (k = 0; k < 8; ++k) 
  * marks t (zeroed by the caller) with ABSOLUTE indices.  beg must be 0 or the first anchor of a (segment, strand) group: there
  * the sequential run has just erased every node from both trees (the `a[i].x>>32 != a[st].x>>32` clause of lchain.c:294,304), st,
  * st_inner and i0 all equal beg, and nothing else is carried over -- so runs of whole groups are independent work items, which
- * is what lets a contig of 10^7 anchors use every host thread (mapper.c: rmq phases). */
+ * is what lets a contig of 10^7 anchors use every host thread (rqphase.c). */
 void mga_lchain_rmq_fwd(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, float pen_gap, float pen_skip,
 						int64_t beg, int64_t end, const mg128_t *a, int32_t *f, int64_t *p, int32_t *v, int32_t *t)
 {

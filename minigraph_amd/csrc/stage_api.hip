@@ -274,7 +274,7 @@ extern "C" int mga_lchain_rescue_batch(int n, const mg128_t *a, const int64_t *a
 	return lchain_batch_impl(n, a, a_off, par, resc, qlen, u, u_off, b, b_off, flag);
 }
 
-// stage test of the RMQ chainer's forward pass (k_rmq.hip): what rq_dev_fwd_hook (mapper.c) allocates and uploads for a chunk, one launch on the default stage stream, f / p / v
+// stage test of the RMQ chainer's forward pass (k_rmq.hip): what rq_dev_fwd_hook (chunk.c) allocates and uploads for a chunk, one launch on the default stage stream, f / p / v
 // and the runs' status back.  A status the kernel never wrote stays 4, as in the pipeline.  tests/test_gpu_rmq.py
 extern "C" int mga_rmq_fwd_batch(int64_t n_total, const mg128_t *a, int n_runs, const int64_t *runs, int n_order, const int32_t *order, int max_dist, int max_dist_inner, int bw,
 								 int max_skip, int cap, float pen_gap, float pen_skip, int32_t *f, int64_t *p, int32_t *v, int32_t *status)

@@ -55,7 +55,7 @@ def run_reference(graph, reads, cigar=True, threads=4, preset="lr"):
 
 def map_with_oracle_stages(graph, reads, occ_max1, lc_max_occ, cigar=True, n_threads=4, preset="lr", per_read=False, return_chains=False, host_dp=False):
     """whole -cx lr (or -cx asm) job: oracle for the kernel stages, product C code for everything on the host.  Under asm the RMQ chainer
-    is the primary chainer and runs in the product's host phases (mapper.c: rq_chain_all) on the oracle's sorted anchors"""
+    is the primary chainer and runs in the product's host phases (rqphase.c: rq_chain_all) on the oracle's sorted anchors"""
     L = mga.load()
     ora = rb.Oracle()
     pp = C.POINTER(C.c_void_p)

@@ -639,7 +639,7 @@ def first_kw(c):
 
 
 def rescue_recipe(ora, c):
-    """mapper.c's host recipe from parts with tests of their own: the oracle's first pass, the condition, mga_ksort_128x over the chained anchors, the host tree with bw_long
+    """the host recipe of batch.c (chain_worker: do_rescue) from parts with tests of their own: the oracle's first pass, the condition, mga_ksort_128x over the chained anchors, the host tree with bw_long
     -> (u, b, due, first-pass u, first-pass b, sorted chained anchors)"""
     u1, b1 = ora.lchain_dp(c.a, **first_kw(c))
     rs = c.rescue

@@ -1,4 +1,4 @@
-"""How a mini-batch is cut into chunks for the pipeline (mapper.c: cut_plan_*): every read exactly once, no chunk above MGA_CHUNK, ramps at the
+"""How a mini-batch is cut into chunks for the pipeline (stream.c: cut_plan_*): every read exactly once, no chunk above MGA_CHUNK, ramps at the
 job's two ends, equal chunks in between (round 5: full chunks + a remainder left chunks of a few hundred reads that pay a pass's whole chain of
 launches for no work).  The GAF never depends on the cut (tests/test_gpu_e2e.py::test_pipeline_knobs_do_not_change_the_output)."""
 import ctypes as C
