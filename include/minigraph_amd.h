@@ -425,6 +425,12 @@ typedef struct {
 	int32_t max_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc;
 	float chn_pen_gap, chn_pen_skip;
 } mga_lchain_par_t;
+/* Where the chaining passes of the long-query path ran (-x asm, ultra-long -x lr reads), as counters since the last reset: [0]-[4] runs of the RMQ chainer's forward pass --
+ * taken by the device, redone on the host for a tie / an inner window beyond the kernel's sort, kept on the host for their length, redone after a failed device call;
+ * [5]-[7] work items of the first-pass DP of ultra-long -x lr reads -- taken by the device, chained on the host for their length or window, redone after a failed device call.
+ * Environment: MGA_DEV_LCDP=1 puts that first pass on the device (k_lcrun.hip); unset or 0 it runs on a host thread, as before.  The device pass shares the buffers of the RMQ
+ * chainer's device pass, so MGA_DEV_RMQ=0 keeps both on the host, whatever MGA_DEV_LCDP says. */
+void mga_rq_dev_stats(int64_t *out, int reset);
 int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par,
 					 uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off);
 /* radix_sort_128x (ksort.h:112-162 through misc.c:9) as the chaining kernels run it: array i = a[a_off[i]..a_off[i+1]) is sorted in place by x with the

@@ -329,6 +329,31 @@ def rmq_fwd_batch(a, runs, order=None, max_dist=10000, max_dist_inner=1000, bw=2
     return f, p, v, status
 
 
+def lcdp_shape():
+    """(wavefronts per workgroup, anchors in the LDS ring) of the workgroup form of k_lcrun.hip"""
+    L = load()
+    nw, ring = C.c_int(0), C.c_int(0)
+    L.mga_dev_lcdp_shape(C.byref(nw), C.byref(ring))
+    return nw.value, ring.value
+
+
+def lcdp_fwd_batch(a, items, max_dist_y=5000, bw=500, max_skip=25, max_iter=5000, pen_gap=0.12, pen_skip=0.0, max_len=1 << 16, wg_min=2048):
+    """the linear chaining DP (mg_lchain_dp's forward loop; k_lcrun.hip) over the work items (beg, end, base, dist_x) of one chunk-level x-sorted anchor array, in one launch:
+    items of at least wg_min anchors get a workgroup, the shorter ones a wavefront -> (f, p, v, status): p counts from the item's base (-1: none), status 0, or 3 for an
+    item left to the host (longer than max_len; workgroup form and max_iter beyond the LDS ring)"""
+    L = load()
+    a = np.ascontiguousarray(a, dtype=m128)
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 4))
+    n, n_items = len(a), len(items)
+    f, p, v = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    status = np.zeros(n_items, dtype=np.int32)
+    L.mga_lcdp_fwd_batch.argtypes = [C.c_int64, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64, C.c_int64, C.c_float, C.c_float] + [C.c_void_p] * 4
+    L.mga_lcdp_fwd_batch.restype = C.c_int
+    _check(L.mga_lcdp_fwd_batch(n, a.ctypes.data, n_items, items.ctypes.data, max_dist_y, bw, max_skip, max_iter, max_len, wg_min, pen_gap, pen_skip,
+                                f.ctypes.data, p.ctypes.data, v.ctypes.data, status.ctypes.data), "mga_lcdp_fwd_batch")
+    return f, p, v, status
+
+
 def gaf_div_batch(div):
     """dv:f: text of each float as the device's GAF writer prints it -> list of bytes"""
     L = load()

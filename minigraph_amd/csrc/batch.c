@@ -96,6 +96,7 @@ void mga_batch_set_rq_device(mga_batch_t *b, mga_rq_dev_fwd_f fwd, void *ctx, ch
 	b->rq_dev_fwd = fwd, b->rq_dev_ctx = ctx, b->rq_harr = harr, b->rq_tot = tot, b->rq_dev_err = 0;
 	pthread_mutex_init(&b->rq_dev_mtx, 0);
 }
+void mga_batch_set_rq_dp_device(mga_batch_t *b, mga_rq_dev_dp_f dp) { b->rq_dev_dp = dp; }
 
 void mga_batch_lchain_par(const mg_idx_t *gi, const mg_mapopt_t *opt, int qlen_max, mga_lchain_par_t *par) /* map-algo.c:377-403 for long reads */
 {

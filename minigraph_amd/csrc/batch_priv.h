@@ -12,6 +12,11 @@
 typedef int (*mga_rq_dev_fwd_f)(void *ctx, int n_reads, const int64_t *r_abs0, const int64_t *r_n, const mg128_t *const *r_a, int32_t *const *r_f, int64_t *const *r_p, int32_t *const *r_v,
 								int n_runs, const int64_t *runs, int n_order, const int32_t *order, int bw, int32_t *status);
 
+/* ... and the one for the first pass of ultra-long -x lr reads (chunk.c: rq_dev_dp_hook, k_lcrun.hip): the linear chaining DP over the work items order[0 .. n_order), longest
+ * first, the first n_wg of them in the workgroup form; items = beg, end, base, dist_x quadruples, chunk-level */
+typedef int (*mga_rq_dev_dp_f)(void *ctx, int n_reads, const int64_t *r_abs0, const int64_t *r_n, const mg128_t *const *r_a, int32_t *const *r_f, int64_t *const *r_p, int32_t *const *r_v,
+							   int n_items, const int64_t *items, int n_order, int n_wg, const int32_t *order, const mga_lchain_par_t *par, int64_t max_len, int32_t *status);
+
 typedef struct {
 	int32_t tid;          /* pool that holds this read's plan */
 	int32_t n_gc;
@@ -46,6 +51,7 @@ struct mga_batch_s {
 	/* round 5: the forward passes of the RMQ chainer on the device (k_rmq.hip), one read at a time on the chunk's stream; rq_harr = pinned arrays p | f | v | t of ALL the
 	 * chunk's anchors (the device writes f, p, v straight into them), rq_tot = their length in anchors */
 	mga_rq_dev_fwd_f rq_dev_fwd;
+	mga_rq_dev_dp_f rq_dev_dp; /* NULL: the first pass of ultra-long -x lr reads stays on a host thread */
 	void *rq_dev_ctx; char *rq_harr; int64_t rq_tot;
 	pthread_mutex_t rq_dev_mtx;
 	int rq_dev_err; char rq_dev_errmsg[256]; /* a device call of the hook failed (not: a run handed back): the chunk fails with this message -- no silent host path */
@@ -80,6 +86,7 @@ void mga_batch_set_want_src(mga_batch_t *b, int on);
 void mga_batch_set_device_chains(mga_batch_t *b, const mga_gc_hdr_t *hdr, const void *gc_pool, const mg_llchain_t *lc_pool, const mg128_t *a_pool);
 void mga_batch_set_device_plan(mga_batch_t *b, const int64_t *chain_off, int32_t *rev, int64_t n_chain);
 void mga_batch_set_rq_device(mga_batch_t *b, mga_rq_dev_fwd_f fwd, void *ctx, char *harr, int64_t tot);
+void mga_batch_set_rq_dp_device(mga_batch_t *b, mga_rq_dev_dp_f dp); /* (after mga_batch_set_rq_device: same context, same pinned arrays) */
 void mga_batch_wfa_export_src(const mga_batch_t *b, mga_wfa_prob_t *prob, char *tseq, mga_plan_src_t *src, int64_t vert_base);
 int64_t mga_batch_n_items(const mga_batch_t *b);
 int64_t mga_batch_n_chains(const mga_batch_t *b);

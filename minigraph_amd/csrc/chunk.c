@@ -68,6 +68,38 @@ static int rq_dev_fwd_hook(void *ctx_, int n_reads, const int64_t *r_abs0, const
 	return 0;
 }
 
+/* ... and the hook for the first pass of ultra-long -x lr reads: the linear chaining DP over work items (k_lcrun.hip).  Only the reads' anchor slices go up -- the marks live
+ * in LDS (workgroup form) or in rq_t as plain scratch (wave form), nothing needs clearing -- through the same pinned staging, with the same single synchronisation. */
+static int rq_dev_dp_hook(void *ctx_, int n_reads, const int64_t *r_abs0, const int64_t *r_n, const mg128_t *const *r_a, int32_t *const *r_f, int64_t *const *r_p, int32_t *const *r_v,
+						  int n_items, const int64_t *items, int n_order, int n_wg, const int32_t *order, const mga_lchain_par_t *par, int64_t max_len, int32_t *status)
+{
+	rq_dev_ctx_t *C = (rq_dev_ctx_t*)ctx_;
+	pipe_ctx_t *P = C->P;
+	mga_sctx_t *sc = P->sc;
+	const int64_t n = C->n_total;
+	char *hs;
+	int x;
+	if (mga_dev_bind_thread() < 0) return -1;
+	if (mga_dbuf_reserve(&P->rq_a, (size_t)n * 16 + 64) < 0 || mga_dbuf_reserve(&P->rq_f, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&P->rq_p, (size_t)n * 8 + 64) < 0 ||
+		mga_dbuf_reserve(&P->rq_v, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&P->rq_t, (size_t)n * 4 + 64) < 0 || mga_dbuf_reserve(&P->rq_cut, (size_t)n_items * 32 + 64) < 0 ||
+		mga_dbuf_reserve(&P->rq_ord, (size_t)n_items * 4 + 64) < 0 || mga_dbuf_reserve(&P->rq_stat, (size_t)n_items * 4 + 64) < 0 || mga_dbuf_reserve(&P->rq_cnt, 64) < 0 ||
+		mga_hbuf_reserve(&P->h_rqs, (size_t)n_items * 40 + 64) < 0) return -1;
+	hs = (char*)P->h_rqs.p; /* items | order | status */
+	memcpy(hs, items, (size_t)n_items * 32); memcpy(hs + (size_t)n_items * 32, order, (size_t)n_order * 4); memcpy(hs + (size_t)n_items * 36, status, (size_t)n_items * 4);
+	for (x = 0; x < n_reads; ++x)
+		if (mga_h2d_s(sc, (mg128_t*)P->rq_a.p + r_abs0[x], r_a[x], (size_t)r_n[x] * 16) < 0) return -1;
+	if (mga_h2d_s(sc, P->rq_cut.p, hs, (size_t)n_items * 32) < 0 || mga_h2d_s(sc, P->rq_ord.p, hs + (size_t)n_items * 32, (size_t)n_order * 4) < 0 ||
+		mga_h2d_s(sc, P->rq_stat.p, hs + (size_t)n_items * 36, (size_t)n_items * 4) < 0) return -1;
+	if (mga_dev_lcdp_fwd(sc, n, (const mg128_t*)P->rq_a.p, n_order, n_wg, P->rq_cut.p, (const int32_t*)P->rq_ord.p, par->max_dist_y, par->bw, par->max_skip, par->max_iter, max_len,
+						 par->chn_pen_gap, par->chn_pen_skip, (int32_t*)P->rq_f.p, (int64_t*)P->rq_p.p, (int32_t*)P->rq_v.p, (int32_t*)P->rq_t.p, (int32_t*)P->rq_stat.p, (int*)P->rq_cnt.p) < 0) return -1;
+	for (x = 0; x < n_reads; ++x)
+		if (mga_d2h_s(sc, r_f[x], (int32_t*)P->rq_f.p + r_abs0[x], (size_t)r_n[x] * 4) < 0 || mga_d2h_s(sc, r_p[x], (int64_t*)P->rq_p.p + r_abs0[x], (size_t)r_n[x] * 8) < 0 ||
+			mga_d2h_s(sc, r_v[x], (int32_t*)P->rq_v.p + r_abs0[x], (size_t)r_n[x] * 4) < 0) return -1;
+	if (mga_d2h_s(sc, hs + (size_t)n_items * 36, P->rq_stat.p, (size_t)n_items * 4) < 0 || mga_ssync(sc) < 0) return -1;
+	memcpy(status, hs + (size_t)n_items * 36, (size_t)n_items * 4);
+	return 0;
+}
+
 /* ---- GAF lines on the device (k_gaf.hip) ----
  * One record per line the reference's writer prints for the chunk (format.c:121-250), in print order: the printed chains of every read (in text mode exactly the chains with a
  * text-kernel chain: chain_id >= 0), or the one line of an unmapped read under MG_M_SHOW_UNMAP.  Returns the number of lines; -1: a read of the chunk has chains but no plan
@@ -119,6 +151,8 @@ typedef struct {
 	int check;          /* MGA_CHECK=1: debugging aid: invariants of what the device stages handed back (host placement) */
 	int dev_splice;     /* MGA_DEV_SPLICE=0: the gaps' targets are spliced on the host and uploaded as bytes (align.h: want_src) */
 	int dev_rmq;        /* MGA_DEV_RMQ=0: the RMQ chainer's forward passes stay on the host threads (k_rmq.hip otherwise) */
+	int dev_lcdp;       /* MGA_DEV_LCDP=1: the first chaining pass of ultra-long -x lr reads on the device, run by run (k_lcrun.hip; it shares the RMQ hook's buffers: not with MGA_DEV_RMQ=0);
+	                     * otherwise on a host thread (hchain.c) */
 	int txt_tight;      /* MGA_TXT_TIGHT=1: a deliberately small text pool, so that a test sees the second launch */
 	int dev_gaf;        /* MGA_DEV_GAF=0: the host formats the GAF lines as in rounds 1-5 (A/B, tests) */
 	int gaf_direct;     /* MGA_GAF_DIRECT=0: a chunk's lines always go through its pieces, never straight to their place in the job's output */
@@ -131,6 +165,7 @@ static void chunk_knobs_read(chunk_knobs_t *k)
 	k->lc_order = env_int("MGA_LC_ORDER", 1), k->dev_gchain_set = s != 0, k->dev_gchain_has = s && *s, k->dev_gchain = k->dev_gchain_has ? atoi(s) : 0;
 	k->host_gchain = env_int("MGA_HOST_GCHAIN", 0), k->dev_gchain_pct = env_int("MGA_DEV_GCHAIN_PCT", 25), k->gc_prof = env_int("MGA_GC_PROF", 0), k->dev_plan = env_int("MGA_DEV_PLAN", 1);
 	k->check = env_int("MGA_CHECK", 0), k->dev_splice = env_int("MGA_DEV_SPLICE", 1), k->dev_rmq = env_int("MGA_DEV_RMQ", 1);
+	k->dev_lcdp = env_int("MGA_DEV_LCDP", 0);
 	k->txt_tight = env_int("MGA_TXT_TIGHT", 0), k->dev_gaf = env_int("MGA_DEV_GAF", 1), k->gaf_direct = env_int("MGA_GAF_DIRECT", 1);
 }
 
@@ -558,6 +593,7 @@ static int chunk_host_chain(chunk_t *c)
 		c->rq_ctx.P = P, c->rq_ctx.opt = c->in.opt, c->rq_ctx.pen_gap = b->pen_gap, c->rq_ctx.pen_skip = b->pen_skip, c->rq_ctx.n_total = c->n_a;
 		CK(mga_hbuf_reserve(&P->h_rq, (size_t)((c->n_a + 1) & ~1LL) * 20 + 64));
 		mga_batch_set_rq_device(b, rq_dev_fwd_hook, &c->rq_ctx, (char*)P->h_rq.p, c->n_a);
+		if (c->chunk_long && c->k.dev_lcdp) mga_batch_set_rq_dp_device(b, rq_dev_dp_hook); /* the first pass too (k_lcrun.hip) */
 	}
 	CK(mga_batch_chain(b, c->h_nmz, c->h_rep, (const int32_t*)P->h_mini.p, c->h_minioff, c->h_nu, c->h_nb, (const uint64_t*)P->h_u.p, (const mg128_t*)P->h_b.p, c->h_aoff, c->chunk_long ? 3 : c->long_q ? 2 : c->is_rmq, c->h_rflag));
 	return 0;

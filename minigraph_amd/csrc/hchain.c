@@ -1,5 +1,5 @@
 /*
- * hchain.c -- backtrack + compaction behind the host RMQ chainer (rmq.c; -x asm and the tied long-join rescues), and the first chaining pass of ULTRA-LONG -x lr reads.
+ * hchain.c -- backtrack + compaction behind the host RMQ chainer (rmq.c; -x asm and the tied long-join rescues), and the first chaining pass of ULTRA-LONG -x lr reads where it stays on the host (k_lcrun.hip otherwise).
  * Reference: lchain.c:9-219.  Everything after the linear chains -- chain records, clean-up, graph chaining -- lives in gc_core.h.
  */
 #include <assert.h>
@@ -84,7 +84,9 @@ mg128_t *mga_compact_a(int32_t n_u, uint64_t *u, int32_t n_v, const int32_t *v, 
  * k_lchain gives a read one wavefront: ~10 k cycles per anchor are hidden by the other reads' wavefronts when a chunk holds thousands of 10 kb reads, but a 5 Mbp read
  * is 3 x 10^5 dependent anchor steps on ONE wavefront ([measured] 1.4 s, round 1-3: slower than the whole reference job).  A host core takes the same steps from its
  * caches in ~0.1 s, and reads of that length are few, so they are placed here -- like the RMQ chainer of -x asm -- while sketch, seeds, WFA and text stay on the device
- * (the long-query path: rqphase.c, rq_fwd_worker).  Fills f, p, v (t: zeroed by the caller); the caller backtracks with mga_chain_backtrack / mga_compact_a. */
+ * (the long-query path: rqphase.c, rq_fwd_worker).  That measurement gave the WHOLE read to one wavefront; the loop's state does not cross an anchor whose predecessor lies on
+ * another (segment, strand) or out of reach, so MGA_DEV_LCDP=1 sends the read's runs through k_lcrun.hip instead (rqphase.c: mga_lcdp_cut) and
+ * this loop takes the whole read only in the other placement -- and, through mga_lchain_dp_fwd_range below, the work items the device hands back.  Fills f, p, v (t: zeroed by the caller); the caller backtracks with mga_chain_backtrack / mga_compact_a. */
 typedef struct { int32_t dist_x, dist_y, bw; float pen_gap, pen_skip; } lcdp_par_t;
 
 static inline int lcdp_pair(const mg128_t *ai, const mg128_t *aj, const lcdp_par_t *P, int32_t *sc_) /* comput_sc (lchain.c:114-139) for one segment: 0 when aj cannot precede ai */
@@ -142,4 +144,14 @@ void mga_lchain_dp_fwd(int max_dist_x, int max_dist_y, int bw, int max_skip, int
 		v[i] = from >= 0 && v[from] > best ? v[from] : best;
 		if (best_in_reach < 0 || (ai->x - a[best_in_reach].x <= (uint64_t)(int64_t)P.dist_x && f[best_in_reach] < best)) best_in_reach = i;
 	}
+}
+
+/* the same loop over the work item [beg, end) of a read (rqphase.c: mga_lcdp_cut; nothing of the loop's state crosses such a cut): the results land in the read's arrays, p
+ * counts from the read's first anchor as the backtrack expects */
+void mga_lchain_dp_fwd_range(int dist_x, int max_dist_y, int bw, int max_skip, int max_iter, float pen_gap, float pen_skip, int64_t beg, int64_t end, const mg128_t *a, int32_t *f,
+							 int64_t *p, int32_t *v, int32_t *t)
+{
+	int64_t i;
+	mga_lchain_dp_fwd(dist_x, max_dist_y, bw, max_skip, max_iter, pen_gap, pen_skip, end - beg, a + beg, f + beg, p + beg, v + beg, t + beg);
+	for (i = beg; i < end; ++i) if (p[i] >= 0) p[i] += beg;
 }

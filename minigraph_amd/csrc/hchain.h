@@ -26,4 +26,11 @@ void mga_rq_tie_stats(int64_t *out, int reset);
 void mga_lchain_dp_fwd(int max_dist_x, int max_dist_y, int bw, int max_skip, int max_iter, float pen_gap, float pen_skip,
 					   int64_t n, const mg128_t *a, int32_t *f, int64_t *p, int32_t *v, int32_t *t);
 
+/* an ultra-long read's x-sorted anchors cut into independent work items of that loop: a boundary wherever the predecessor in x order lies on another (segment, strand) or
+ * more than dist_x = max(max_dist_x, bw) behind -- nothing of the loop's state crosses it (k_lcrun.hip) -- kept only where the item before it holds at least run_min anchors.
+ * *cuts: malloc'ed, cuts[0] = 0 .. cuts[*n_cut] = n.  mga_lchain_dp_fwd_range: the loop over [beg, end) of the read's arrays, p relative to the read (t zeroed over the range) */
+void mga_lcdp_cut(int64_t n, const mg128_t *a, int dist_x, int64_t run_min, int64_t **cuts, int32_t *n_cut);
+void mga_lchain_dp_fwd_range(int dist_x, int max_dist_y, int bw, int max_skip, int max_iter, float pen_gap, float pen_skip, int64_t beg, int64_t end, const mg128_t *a, int32_t *f,
+							 int64_t *p, int32_t *v, int32_t *t);
+
 #endif

@@ -299,6 +299,18 @@ typedef struct { int64_t beg, end, base; } mga_rq_run_t;
 int mga_dev_rmq_fwd(mga_sctx_t *sc, int64_t n_total, const mg128_t *d_a, int n_order, const void *d_runs, const int32_t *d_order, int max_dist, int max_dist_inner, int bw,
 					int max_skip, int cap, float pen_gap, float pen_skip, int32_t *d_f, int64_t *d_p, int32_t *d_v, int32_t *d_t, double *d_pri, int32_t *d_ys,
 					int32_t *d_status, int *d_counter);
+/* the linear chaining DP (mg_lchain_dp's forward loop, lchain.c:168-207) over work items of a CHUNK's x-sorted anchors (k_lcrun.hip): d_items = array of
+ * { int64 beg, end, base, dist_x } (as above; dist_x = max(max_dist_x, bw) of the item's read), taken in the order d_order lists them, longest first; the first n_wg of the
+ * order get a workgroup each, the others a wavefront.  d_status[r] = 0, or 3 when the host has to chain the item (longer than max_len; a workgroup-form item whose max_iter
+ * the LDS ring does not hold); p[] comes out relative to `base`.  Scratch: d_t (n_total int32, no need to clear it), d_counter */
+typedef struct { int64_t beg, end, base, dist_x; } mga_lcdp_item_t;
+int mga_dev_lcdp_fwd(mga_sctx_t *sc, int64_t n_total, const mg128_t *d_a, int n_order, int n_wg, const void *d_items, const int32_t *d_order, int max_dist_y, int bw,
+					 int max_skip, int max_iter, int64_t max_len, float pen_gap, float pen_skip, int32_t *d_f, int64_t *d_p, int32_t *d_v, int32_t *d_t, int32_t *d_status, int *d_counter);
+void mga_dev_lcdp_shape(int *nw, int *ring); /* wavefronts of the workgroup form, anchors its ring holds */
+/* stage test of the above: n_items quadruples over a[n_total]; the kernel takes the items of at most max_len anchors, longest first, those of at least wg_min anchors in the
+ * workgroup form; status 3 for the others and for what the kernel hands back */
+int mga_lcdp_fwd_batch(int64_t n_total, const mg128_t *a, int n_items, const int64_t *items, int max_dist_y, int bw, int max_skip, int max_iter, int64_t max_len, int64_t wg_min,
+					   float pen_gap, float pen_skip, int32_t *f, int64_t *p, int32_t *v, int32_t *status);
 /* stage tests (stage_api.hip; host pointers in and out).  mga_rmq_fwd_batch: the launch above over n_runs triples { beg, end, base } of the x-sorted chunk array a[n_total];
  * order: n_order run indices, or NULL for the table's order (n_order is then n_runs).  Out: f, p, v per anchor (zero where no run wrote), status per run, 4 where the kernel
  * never came.  mga_lchain_rescue_batch: mga_lchain_batch with the long-join rescue switched on: qlen[n] query lengths in, flag[n] (0 / 1 / 2, see mga_dev_lchain) out. */

@@ -14,6 +14,9 @@ typedef struct { int32_t read, k; } rq_task_t;
 #define RQ_RUN_MIN 16384 /* anchors per work item, at least */
 #define RQ_RUN_MIN_DEV 1024 /* ... of the device pass: a wavefront per run, thousands of them */
 #define RQ_RUN_MAX_DEV (1 << 20) /* a run beyond this is the host's: one wavefront walks a run anchor by anchor */
+#define RQ_DP_WG_MIN 2048       /* work items of the first-pass DP of at least this many anchors get a workgroup, the shorter ones a wavefront (k_lcrun.hip) */
+#define RQ_DP_MAX_DEV (1 << 16)  /* ... of the first-pass DP of ultra-long -x lr reads (k_lcrun.hip): a workgroup takes its run anchor by anchor too, three barriers each, and a launch lasts
+                                  * as long as its longest item; a read inside ONE long segment is a single run of 10^5 anchors and more, which a host core takes from its caches */
 
 static void rq_cut(rq_read_t *r, int64_t run_min)
 {
@@ -27,6 +30,31 @@ static void rq_cut(rq_read_t *r, int64_t run_min)
 			r->cut[++r->n_cut] = i, last = i;
 		}
 	r->cut[++r->n_cut] = r->n;
+}
+
+/* The first pass of an ultra-long -x lr read is the DP, not the RMQ chainer, and its independent pieces are finer: the forward loop's state (hchain.c: lo, best_in_reach, the
+ * marks) does not survive an anchor whose predecessor in x order lies on another (segment, strand) or more than dist_x behind it -- the window is empty there, best_in_reach
+ * becomes the anchor itself, marks are only written below the cut.  Any subset of these boundaries is a valid cut set (an item of several runs is chained through). */
+void mga_lcdp_cut(int64_t n, const mg128_t *a, int dist_x, int64_t run_min, int64_t **cuts, int32_t *n_cut)
+{
+	int64_t i, last = 0, *cut;
+	int32_t m = 16, nc = 0;
+	cut = MGA_MALLOC(int64_t, m + 1);
+	cut[0] = 0;
+	for (i = 1; i < n; ++i)
+		if ((a[i].x >> 32 != a[i - 1].x >> 32 || a[i].x > a[i - 1].x + (uint64_t)(int64_t)dist_x) && i - last >= run_min) {
+			if (nc + 1 == m) { m <<= 1; cut = MGA_REALLOC(int64_t, cut, m + 1); }
+			cut[++nc] = i, last = i;
+		}
+	cut[++nc] = n > 0 ? n : 0;
+	*cuts = cut, *n_cut = nc;
+}
+
+static void rq_dp_par(const mga_batch_t *b, int read, mga_lchain_par_t *par) /* mg_lchain_dp's parameters for this read (map-algo.c:377-403) */
+{
+	const mg_mapopt_t *opt = &b->opt;
+	mga_batch_lchain_par(b->gi, opt, 0, par);
+	if (opt->max_gap_ref <= 0 && opt->max_frag_len > 0) { const int g = opt->max_frag_len - b->qlens[read]; par->max_dist_x = g > opt->max_gap ? g : opt->max_gap; } /* -F: map-algo.c:383-386 */
 }
 
 static void rq_arrays(mga_batch_t *b, rq_read_t *r, int64_t i)
@@ -53,7 +81,11 @@ static void rq_prepare_worker_(void *data, int64_t i, int tid)
 	if (r->n <= 0) return;
 	r->a = (mg128_t*)(b->a + b->a_off[i]); /* every read owns its slice of the staging buffer */
 	if ((b->a_is_raw == 2 || b->a_is_raw == 3) && r->n > 1) mga_ksort_128x(r->n, r->a); /* hit order from the device: radix_sort_128x (map-algo.c:189) */
-	if (b->a_is_raw == 3 || b->a_is_raw == 5) { /* (5: already sorted -- the CPU tests' oracle anchors) */ r->cut = MGA_MALLOC(int64_t, 2); r->cut[0] = 0, r->cut[1] = r->n, r->n_cut = 1; } /* an ultra-long -x lr read: its first pass is the DP, one work item */
+	if (b->a_is_raw == 3 && b->rq_dev_fwd && b->rq_dev_dp) { /* an ultra-long -x lr read whose first pass, the DP, goes through the device: work items of >= RQ_RUN_MIN_DEV anchors (k_lcrun.hip) */
+		mga_lchain_par_t par;
+		rq_dp_par(b, (int)i, &par);
+		mga_lcdp_cut(r->n, r->a, par.max_dist_x > par.bw ? par.max_dist_x : par.bw, RQ_RUN_MIN_DEV, &r->cut, &r->n_cut);
+	} else if (b->a_is_raw == 3 || b->a_is_raw == 5) { /* (5: already sorted -- the CPU tests' oracle anchors) */ r->cut = MGA_MALLOC(int64_t, 2); r->cut[0] = 0, r->cut[1] = r->n, r->n_cut = 1; } /* ... on a host thread: one work item */
 	else rq_cut(r, b->rq_dev_fwd ? RQ_RUN_MIN_DEV : RQ_RUN_MIN);
 	rq_arrays(b, r, i);
 	CPU_ADD(C_LCCOPY, tc);
@@ -69,9 +101,8 @@ static void rq_fwd_worker(void *data, int64_t j, int tid)
 	(void)tid;
 	if ((b->a_is_raw == 3 || b->a_is_raw == 5) && !r->pass2) { /* mg_lchain_dp (map-algo.c:393-403) on this host thread: hchain.c */
 		mga_lchain_par_t par;
-		mga_batch_lchain_par(b->gi, opt, 0, &par);
-		if (opt->max_gap_ref <= 0 && opt->max_frag_len > 0) { const int g = opt->max_frag_len - b->qlens[task->read]; par.max_dist_x = g > opt->max_gap ? g : opt->max_gap; } /* -F: map-algo.c:383-386 */
-		mga_lchain_dp_fwd(par.max_dist_x, par.max_dist_y, par.bw, par.max_skip, par.max_iter, par.chn_pen_gap, par.chn_pen_skip, r->n, r->a, r->f, r->p, r->v, r->t);
+		rq_dp_par(b, task->read, &par);
+		mga_lchain_dp_fwd_range(par.max_dist_x, par.max_dist_y, par.bw, par.max_skip, par.max_iter, par.chn_pen_gap, par.chn_pen_skip, r->cut[task->k], r->cut[task->k + 1], r->a, r->f, r->p, r->v, r->t); /* (one item, the whole read, unless the read was cut for the device) */
 	} else
 	mga_lchain_rmq_fwd(opt->max_gap, opt->max_gap_pre, r->pass2 ? opt->bw_long : opt->bw, opt->max_lc_skip, opt->rmq_size_cap, b->pen_gap, b->pen_skip,
 					   r->cut[task->k], r->cut[task->k + 1], r->a, r->f, r->p, r->v, r->t);
@@ -79,14 +110,16 @@ static void rq_fwd_worker(void *data, int64_t j, int tid)
 }
 
 /* runs of the RMQ chainer's forward pass: [0] taken by the device, [1] redone on the host because two candidates tied on the priority (the AVL shape decides: k_rmq.hip),
- * [2] ... because the inner window held more candidates than the kernel sorts, [3] kept on the host for their length, [4] device call failed */
+ * [2] ... because the inner window held more candidates than the kernel sorts, [3] kept on the host for their length, [4] device call failed;
+ * work items of the first-pass DP of ultra-long -x lr reads (k_lcrun.hip): [5] taken by the device, [6] chained on the host for their length or window, [7] device call failed */
 static int64_t g_rq_dev_stat[8];
 void mga_rq_dev_stats(int64_t *out, int reset) { int k; for (k = 0; k < 8; ++k) { out[k] = __atomic_load_n(&g_rq_dev_stat[k], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_rq_dev_stat[k], 0, __ATOMIC_RELAXED); } }
 
 typedef struct { int64_t len; int32_t k; } rq_ord_t;
 static int rq_ord_cmp(const void *x, const void *y) { const rq_ord_t *p = (const rq_ord_t*)x, *q = (const rq_ord_t*)y; return p->len > q->len ? -1 : p->len < q->len ? 1 : (p->k > q->k) - (p->k < q->k); }
 
-static int rq_use_dev(const mga_batch_t *b, const rq_read_t *r) { return b->rq_dev_fwd != 0 && !((b->a_is_raw == 3 || b->a_is_raw == 5) && !r->pass2); }
+static int rq_first_dp(const mga_batch_t *b, const rq_read_t *r) { return (b->a_is_raw == 3 || b->a_is_raw == 5) && !r->pass2; } /* this pass of the read is the DP */
+static int rq_use_dev(const mga_batch_t *b, const rq_read_t *r) { return b->rq_dev_fwd != 0 && (!rq_first_dp(b, r) || (b->a_is_raw == 3 && b->rq_dev_dp != 0)); }
 
 /* the forward pass of ALL runs of some reads' current pass (the same pass for all of them): on the device, a wavefront per run, ONE launch for all the reads (k_rmq.hip:
  * a launch lasts as long as its longest run, and a read's ~2 000 runs fill a quarter of the wave slots); what the device gives back -- a run with tied priorities, an inner
@@ -94,23 +127,26 @@ static int rq_use_dev(const mga_batch_t *b, const rq_read_t *r) { return b->rq_d
 static void rq_dev_worker(mga_batch_t *b, int n_reads, const int32_t *reads)
 {
 	const mg_mapopt_t *opt = &b->opt;
-	const int pass2 = b->rq[reads[0]].pass2;
-	int64_t n_runs = 0, k, q, *runs, *abs0, *rn, cnt[5] = { 0, 0, 0, 0, 0 }, tc = cpu_now();
+	const int pass2 = b->rq[reads[0]].pass2, dp = rq_first_dp(b, &b->rq[reads[0]]), W = dp ? 4 : 3; /* dp: the first pass of ultra-long -x lr reads, items = beg, end, base, dist_x */
+	mga_lchain_par_t par, *rpar = 0; /* dp: per read (-F moves max_dist_x) */
+	int64_t n_runs = 0, k, q, *runs, *abs0, *rn, cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, tc = cpu_now();
 	const mg128_t **ra; int32_t **rf, **rv; int64_t **rp;
 	rq_ord_t *ord;
 	int32_t *order, *status, n_dev = 0;
-	int rc = 0, x;
+	int rc = 0, x, n_wg = 0;
 	for (x = 0; x < n_reads; ++x) n_runs += b->rq[reads[x]].n_cut;
-	runs = MGA_MALLOC(int64_t, 3 * n_runs + 3); ord = MGA_MALLOC(rq_ord_t, n_runs + 1); order = MGA_MALLOC(int32_t, n_runs + 1); status = MGA_MALLOC(int32_t, n_runs + 1);
+	runs = MGA_MALLOC(int64_t, W * n_runs + 4); ord = MGA_MALLOC(rq_ord_t, n_runs + 1); order = MGA_MALLOC(int32_t, n_runs + 1); status = MGA_MALLOC(int32_t, n_runs + 1);
 	abs0 = MGA_MALLOC(int64_t, n_reads); rn = MGA_MALLOC(int64_t, n_reads); ra = (const mg128_t**)MGA_MALLOC(void*, n_reads); rf = (int32_t**)MGA_MALLOC(void*, n_reads);
 	rv = (int32_t**)MGA_MALLOC(void*, n_reads); rp = (int64_t**)MGA_MALLOC(void*, n_reads);
+	if (dp) { rpar = MGA_MALLOC(mga_lchain_par_t, n_reads); for (x = 0; x < n_reads; ++x) rq_dp_par(b, reads[x], &rpar[x]); par = rpar[0]; }
 	for (x = 0, q = 0; x < n_reads; ++x) {
 		rq_read_t *r = &b->rq[reads[x]];
 		abs0[x] = b->a_off[reads[x]] - b->a_off[0], rn[x] = r->n, ra[x] = r->a, rf[x] = r->f, rv[x] = r->v, rp[x] = r->p;
 		for (k = 0; k < r->n_cut; ++k, ++q) {
-			runs[3 * q] = abs0[x] + r->cut[k], runs[3 * q + 1] = abs0[x] + r->cut[k + 1], runs[3 * q + 2] = abs0[x];
+			runs[W * q] = abs0[x] + r->cut[k], runs[W * q + 1] = abs0[x] + r->cut[k + 1], runs[W * q + 2] = abs0[x];
+			if (dp) runs[W * q + 3] = rpar[x].max_dist_x > rpar[x].bw ? rpar[x].max_dist_x : rpar[x].bw;
 			status[q] = 3;
-			if (r->cut[k + 1] - r->cut[k] <= RQ_RUN_MAX_DEV) ord[n_dev].len = r->cut[k + 1] - r->cut[k], ord[n_dev++].k = (int32_t)q;
+			if (r->cut[k + 1] - r->cut[k] <= (dp ? RQ_DP_MAX_DEV : RQ_RUN_MAX_DEV)) ord[n_dev].len = r->cut[k + 1] - r->cut[k], ord[n_dev++].k = (int32_t)q;
 		}
 	}
 	qsort(ord, (size_t)n_dev, sizeof *ord, rq_ord_cmp); /* longest first: a launch lasts as long as its longest run */
@@ -119,24 +155,34 @@ static void rq_dev_worker(mga_batch_t *b, int n_reads, const int32_t *reads)
 		const double tw0 = mga_wtime();
 		pthread_mutex_lock(&b->rq_dev_mtx);
 		const double tw1 = mga_wtime();
+		if (dp) {
+			while (n_wg < n_dev && ord[n_wg].len >= RQ_DP_WG_MIN) ++n_wg; /* (longest first: a prefix) */
+			rc = b->rq_dev_dp(b->rq_dev_ctx, n_reads, abs0, rn, ra, rf, rp, rv, (int)n_runs, runs, n_dev, n_wg, order, &par, RQ_DP_MAX_DEV, status);
+		} else
 		rc = b->rq_dev_fwd(b->rq_dev_ctx, n_reads, abs0, rn, ra, rf, rp, rv, (int)n_runs, runs, n_dev, order, pass2 ? opt->bw_long : opt->bw, status);
 		if (rc < 0 && !b->rq_dev_err) { b->rq_dev_err = 1; snprintf(b->rq_dev_errmsg, sizeof b->rq_dev_errmsg, "%s", mga_last_error()); } /* (the message is this thread's) */
 		pthread_mutex_unlock(&b->rq_dev_mtx);
-		if (g_cpu_on) fprintf(stderr, "[rq] pass %d of %d reads: %d runs (longest %ld anchors) through the device in %.1f ms (+ %.1f ms waiting for it)\n", pass2 + 1, n_reads, n_dev, (long)ord[0].len, (mga_wtime() - tw1) * 1e3, (tw1 - tw0) * 1e3);
+		if (g_cpu_on) fprintf(stderr, "[rq] pass %d%s of %d reads: %d of %ld runs (longest %ld anchors, %d as workgroups) through the device in %.1f ms (+ %.1f ms waiting for it)\n", pass2 + 1, dp ? " (DP)" : "", n_reads, n_dev, (long)n_runs, (long)ord[0].len, n_wg, (mga_wtime() - tw1) * 1e3, (tw1 - tw0) * 1e3);
 		if (rc < 0) for (k = 0; k < n_dev; ++k) status[order[k]] = 4; /* (the task graph runs to its end on the host's tree; mga_batch_chain() then FAILS the chunk with the device's message) */
 	}
 	for (x = 0, q = 0; x < n_reads; ++x) {
 		rq_read_t *r = &b->rq[reads[x]];
 		for (k = 0; k < r->n_cut; ++k, ++q) {
-			if (status[q] == 0) { ++cnt[0]; continue; }
-			++cnt[status[q] <= 4 ? status[q] : 4];
+			if (status[q] == 0) { ++cnt[dp ? 5 : 0]; continue; }
 			memset(r->t + r->cut[k], 0, (size_t)(r->cut[k + 1] - r->cut[k]) * 4); /* the marks of a run stay inside it */
+			if (dp) { /* the host's loop over the item, inside the read's arrays */
+				const mga_lchain_par_t *P = &rpar[x];
+				++cnt[status[q] == 3 ? 6 : 7];
+				mga_lchain_dp_fwd_range(P->max_dist_x, P->max_dist_y, P->bw, P->max_skip, P->max_iter, P->chn_pen_gap, P->chn_pen_skip, r->cut[k], r->cut[k + 1], r->a, r->f, r->p, r->v, r->t);
+				continue;
+			}
+			++cnt[status[q] <= 4 ? status[q] : 4];
 			mga_lchain_rmq_fwd(opt->max_gap, opt->max_gap_pre, pass2 ? opt->bw_long : opt->bw, opt->max_lc_skip, opt->rmq_size_cap, b->pen_gap, b->pen_skip,
 							   r->cut[k], r->cut[k + 1], r->a, r->f, r->p, r->v, r->t);
 		}
 	}
-	for (k = 0; k < 5; ++k) if (cnt[k]) __atomic_fetch_add(&g_rq_dev_stat[k], cnt[k], __ATOMIC_RELAXED);
-	free(runs); free(ord); free(order); free(status); free(abs0); free(rn); free((void*)ra); free(rf); free(rv); free(rp);
+	for (k = 0; k < 8; ++k) if (cnt[k]) __atomic_fetch_add(&g_rq_dev_stat[k], cnt[k], __ATOMIC_RELAXED);
+	free(rpar); free(runs); free(ord); free(order); free(status); free(abs0); free(rn); free((void*)ra); free(rf); free(rv); free(rp);
 	CPU_ADD(pass2 ? C_LCRESCUE : C_LCCOPY, tc);
 }
 
@@ -283,7 +329,7 @@ void rq_chain_all(mga_batch_t *b)
 	b->rq = MGA_CALLOC(rq_read_t, b->n > 0 ? b->n : 1);
 	t[0] = mga_wtime();
 	if (getenv("MGA_RQ_BARRIERS") && atoi(getenv("MGA_RQ_BARRIERS")) > 0) {
-		b->rq_dev_fwd = 0; /* (the A/B form with barriers between the phases is the host's) */
+		b->rq_dev_fwd = 0, b->rq_dev_dp = 0; /* (the A/B form with barriers between the phases is the host's: no device pass, no cut for one) */
 		mga_parallel_for(b->n_threads, b->n, rq_prepare_worker, b);
 		t[1] = mga_wtime();
 		rq_run_fwd(b, 0);

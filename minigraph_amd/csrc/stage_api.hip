@@ -307,6 +307,43 @@ extern "C" int mga_rmq_fwd_batch(int64_t n_total, const mg128_t *a, int n_runs, 
 	return 0;
 }
 
+// stage test of the first-pass DP of ultra-long -x lr reads (k_lcrun.hip): what rq_dev_worker (rqphase.c) and rq_dev_dp_hook (chunk.c) do for a chunk -- the items of at most
+// max_len anchors listed longest first, those of at least wg_min anchors in the workgroup form, the others' status preset to 3 -- one launch, f / p / v and the statuses back.
+// tests/test_gpu_lcdp.py
+extern "C" int mga_lcdp_fwd_batch(int64_t n_total, const mg128_t *a, int n_items, const int64_t *items, int max_dist_y, int bw, int max_skip, int max_iter, int64_t max_len, int64_t wg_min,
+								  float pen_gap, float pen_skip, int32_t *f, int64_t *p, int32_t *v, int32_t *status)
+{
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	if (n_total < 0 || n_items < 0 || n_total >= 0x7fffffffLL || max_iter < 1 || bw < 0) { mga_set_error("lcdp_fwd_batch: bad sizes"); return -1; }
+	std::vector<int32_t> order;
+	std::vector<char> seen((size_t)n_total + 1, 0);
+	for (int r = 0; r < n_items; ++r) { // the kernel trusts its table: inside the array, disjoint, a positive reach
+		const int64_t beg = items[4 * r], end = items[4 * r + 1], base = items[4 * r + 2], dist_x = items[4 * r + 3];
+		if (!(0 <= base && base <= beg && beg <= end && end <= n_total) || dist_x < 1 || dist_x > 0x7fffffffLL) { mga_set_error("lcdp_fwd_batch: item %d lies outside the %ld anchors", r, (long)n_total); return -1; }
+		for (int64_t i = beg; i < end; ++i) { if (seen[(size_t)i]) { mga_set_error("lcdp_fwd_batch: item %d overlaps another", r); return -1; } seen[(size_t)i] = 1; }
+		status[r] = 3;
+		if (end - beg <= max_len) order.push_back(r), status[r] = 4;
+	}
+	std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return items[4 * x + 1] - items[4 * x] > items[4 * y + 1] - items[4 * y]; });
+	int n_wg = 0;
+	while (n_wg < (int)order.size() && items[4 * order[n_wg] + 1] - items[4 * order[n_wg]] >= wg_min) ++n_wg;
+	if (n_total > 0) { memset(f, 0, (size_t)n_total * 4); memset(p, 0, (size_t)n_total * 8); memset(v, 0, (size_t)n_total * 4); }
+	if (n_total == 0 || order.empty()) return 0;
+	const size_t n = (size_t)n_total;
+	dptr d_a, d_f, d_p, d_v, d_t, d_items, d_ord, d_stat, d_cnt;
+	if (!d_a.alloc(n * 16 + 64) || !d_f.alloc(n * 4 + 64) || !d_p.alloc(n * 8 + 64) || !d_v.alloc(n * 4 + 64) || !d_t.alloc(n * 4 + 64) || !d_items.alloc((size_t)n_items * 32 + 64) ||
+		!d_ord.alloc((size_t)n_items * 4 + 64) || !d_stat.alloc((size_t)n_items * 4 + 64) || !d_cnt.alloc(64)) return -1;
+	if (mga_h2d(d_a.p, a, n * 16) < 0 || mga_h2d(d_items.p, items, (size_t)n_items * 32) < 0 || mga_h2d(d_stat.p, status, (size_t)n_items * 4) < 0 ||
+		mga_h2d(d_ord.p, order.data(), order.size() * 4) < 0) return -1;
+	if (mga_dmemset_s(SC, d_f.p, 0, n * 4) < 0 || mga_dmemset_s(SC, d_p.p, 0, n * 8) < 0 || mga_dmemset_s(SC, d_v.p, 0, n * 4) < 0) return -1;
+	if (mga_dev_lcdp_fwd(SC, n_total, d_a.as<mg128_t>(), (int)order.size(), n_wg, d_items.p, d_ord.as<int32_t>(), max_dist_y, bw, max_skip, max_iter, max_len, pen_gap, pen_skip,
+						 d_f.as<int32_t>(), d_p.as<int64_t>(), d_v.as<int32_t>(), d_t.as<int32_t>(), d_stat.as<int32_t>(), (int*)d_cnt.p) < 0) return -1;
+	if (mga_ssync(SC) < 0 || mga_d2h(f, d_f.p, n * 4) < 0 || mga_d2h(p, d_p.p, n * 8) < 0 || mga_d2h(v, d_v.p, n * 4) < 0 || mga_d2h(status, d_stat.p, (size_t)n_items * 4) < 0) return -1;
+	return 0;
+}
+
 // mg_cov_map (cal_cov.c:8-53) for flat chain records through k_cov.hip against gi's graph replica; ADDS into seg_bases[n_seg] / link_cnt[n_arc] / *st
 extern "C" int mga_cov_batch(const mg_idx_t *gi, int n_chain, const mga_cov_chain_t *chain, int64_t n_vert, const uint32_t *vert, int32_t min_mapq, int32_t min_blen,
 							 int64_t *seg_bases, int64_t *link_cnt, mga_cov_stats_t *st)
