@@ -431,6 +431,27 @@ typedef struct {
  * Environment: MGA_DEV_LCDP=1 puts that first pass on the device (k_lcrun.hip); unset or 0 it runs on a host thread, as before.  The device pass shares the buffers of the RMQ
  * chainer's device pass, so MGA_DEV_RMQ=0 keeps both on the host, whatever MGA_DEV_LCDP says. */
 void mga_rq_dev_stats(int64_t *out, int reset);
+/* The bridge between two linear chains as a stage of its own: the graph wavefront aligner (gfa_ed_init / gfa_ed_step as gchain1.c:349-381 calls them) of q[0..ql) from
+ * (v0, off0) to (v1, off1).  mga_gwfa_bridge runs on the calling thread: the edit distance (-1: not reached within s_term edits) and the malloc'ed vertex walk.
+ * mga_gwfa_bridge_batch runs n such problems on the device against gi's graph replica: prob[i].q_off is where problem i's query lies in qseq; form MGA_GWFA_FORM_WAVE gives
+ * every problem a wavefront (the routine of k_gchain_p2), MGA_GWFA_FORM_WG a workgroup of 8 wavefronts with the wavefronts of cells in LDS (k_gwfa_wg.hip) -- a problem
+ * that form cannot hold (more than 1 024 cells in a wavefront, ...) comes back and is redone by the wave form.  Out, per problem: ed[i], n_path[i], the walk at
+ * path + i * path_cap, status[i] (which form served it), peak[i] (largest wavefront of cells the workgroup form saw; 0 in the wave form).
+ * Environment of the mapping path: MGA_GC_BRIDGE_WG=1 (with MGA_GC_SPLIT=1) sends the bridges over query gaps of at least 600 bases to the workgroup form in a launch of their
+ * own in front of k_gchain_p2; unset or 0: as before.  mga_gc_wg_stats: out[0] bridges that form served, out[1] bridges it handed back, since the last reset. */
+typedef struct { int64_t q_off; int32_t ql; uint32_t v0; int32_t off0; uint32_t v1; int32_t off1, max_lag, s_term, pad; } mga_gwfa_prob_t;
+#define MGA_GWFA_FORM_WAVE 0
+#define MGA_GWFA_FORM_WG   1
+#define MGA_GWFA_WG     0   /* status: served by the workgroup form */
+#define MGA_GWFA_BACK   1   /* handed back by the workgroup form, served by the wave form */
+#define MGA_GWFA_WAVE   2   /* served by the wave form, as asked */
+#define MGA_GWFA_E_ROOM 3   /* not served: the walk is longer than path_cap, or the scratch arena was too small (ed = -1, no walk) */
+int32_t mga_gwfa_bridge(const gfa_t *g, const gfa_edseq_t *es, int32_t ql, const char *q, uint32_t v0, int32_t off0, uint32_t v1, int32_t off1,
+						int32_t max_lag, int32_t s_term, int32_t **path, int32_t *nv);
+int mga_gwfa_bridge_batch(const mg_idx_t *gi, int n, const char *qseq, int64_t n_q, const mga_gwfa_prob_t *prob, int form, int32_t path_cap,
+						  int32_t *ed, int32_t *n_path, int32_t *path, int32_t *status, int32_t *peak);
+void mga_gwfa_wg_shape(int *nw, int *cells); /* wavefronts of the workgroup form, cells its wavefront buffers hold */
+void mga_gc_wg_stats(int64_t *out, int reset);
 int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par,
 					 uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off);
 /* radix_sort_128x (ksort.h:112-162 through misc.c:9) as the chaining kernels run it: array i = a[a_off[i]..a_off[i+1]) is sorted in place by x with the

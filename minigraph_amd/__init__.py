@@ -354,6 +354,44 @@ def lcdp_fwd_batch(a, items, max_dist_y=5000, bw=500, max_skip=25, max_iter=5000
     return f, p, v, status
 
 
+gwfa_prob_dtype = np.dtype([("q_off", "<i8"), ("ql", "<i4"), ("v0", "<u4"), ("off0", "<i4"), ("v1", "<u4"), ("off1", "<i4"), ("max_lag", "<i4"), ("s_term", "<i4"),
+                            ("pad", "<i4")])   # mga_gwfa_prob_t
+GWFA_STATUS = {0: "workgroup", 1: "handed back", 2: "wave", 3: "no room"}
+
+
+def gwfa_wg_shape():
+    """(wavefronts per workgroup, cells a wavefront buffer holds) of the workgroup form of the bridge (k_gwfa_wg.hip)"""
+    nw, cells = C.c_int(0), C.c_int(0)
+    load().mga_gwfa_wg_shape(C.byref(nw), C.byref(cells))
+    return nw.value, cells.value
+
+
+def gwfa_bridge_batch(graph, problems, form="workgroup", path_cap=4096):
+    """the bridge between two linear chains (graph wavefront alignment) for n problems (query bytes, v0, off0, v1, off1, max_lag, s_term) on the device against the
+    graph's replica; form "wave": a wavefront per problem, "workgroup": 8 wavefronts per problem with the cells in LDS, what that form cannot hold going through the
+    wave form -> list of (ed, path vertices, status, peak): ed -1 = not reached, status a key of GWFA_STATUS, peak = largest wavefront of cells (workgroup form)"""
+    L = load()
+    n = len(problems)
+    qseq, q_off = concat([p[0] for p in problems])
+    prob = np.zeros(n, dtype=gwfa_prob_dtype)
+    for i, (q, v0, off0, v1, off1, max_lag, s_term) in enumerate(problems):
+        prob[i] = (q_off[i], len(q), v0, off0, v1, off1, max_lag, s_term, 0)
+    ed, n_path, status, peak = (np.zeros(n, dtype=np.int32) for _ in range(4))
+    path = np.zeros((max(n, 1), path_cap), dtype=np.int32)
+    L.mga_gwfa_bridge_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_int, C.c_int32] + [C.c_void_p] * 5
+    L.mga_gwfa_bridge_batch.restype = C.c_int
+    _check(L.mga_gwfa_bridge_batch(graph.gi, n, qseq, len(qseq), prob.ctypes.data, {"wave": 0, "workgroup": 1}[form], path_cap,
+                                   ed.ctypes.data, n_path.ctypes.data, path.ctypes.data, status.ctypes.data, peak.ctypes.data), "mga_gwfa_bridge_batch")
+    return [(int(ed[i]), [int(x) for x in path[i, :n_path[i]]], int(status[i]), int(peak[i])) for i in range(n)]
+
+
+def gc_wg_stats(reset=False):
+    """bridges of the mapping path that the workgroup form (MGA_GC_BRIDGE_WG=1) served / handed back since the last reset"""
+    st = (C.c_int64 * 2)()
+    load().mga_gc_wg_stats(st, 1 if reset else 0)
+    return {"served": st[0], "handed_back": st[1]}
+
+
 def gaf_div_batch(div):
     """dv:f: text of each float as the device's GAF writer prints it -> list of bytes"""
     L = load()

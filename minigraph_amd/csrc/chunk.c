@@ -183,7 +183,7 @@ typedef struct { /* one run of the stage sequence: a stack object of map_chunk()
 	/* counts */
 	int64_t tot, n_mz, n_a, n_mini, n_prob, n_tb;
 	unsigned long long ptot[8]; /* device-made gap list: printed chains, plan items, problems, walk vertices, target bytes, query bases, overflow flag */
-	unsigned long long ctl[9];  /* k_gchain's counters: [1] [2] [6] records used in the three pools, [3] reads to retry, [4] [5] GWFA / shortest-k calls, [7] arena peak, [8] GWFA calls / graph searches that ran in the LDS scratch */
+	unsigned long long ctl[11]; /* [9] [10] bridges the workgroup form served / handed back (k_gwfa_wg.hip); k_gchain's counters: [1] [2] [6] records used in the three pools, [3] reads to retry, [4] [5] GWFA / shortest-k calls, [7] arena peak, [8] GWFA calls / graph searches that ran in the LDS scratch */
 	int64_t gc_cap, lc_cap, ga_cap; /* ... and the pools' capacities */
 	int64_t dp_chain, dp_item, dp_prob, dp_vert, dp_tb, hp_prob, hp_tb; /* the device-made gap list (dev_plan) comes first in every array; what the host threads planned (all reads, or with dev_plan the few reads chained here) follows */
 	int64_t n_item, n_chain, n_vert, n_ops, cells; unsigned long long txt_used;
@@ -471,7 +471,7 @@ static int gchain_run(chunk_t *c)
 		CK(mga_dmemset_s(sc, P->gcctl.p, 0, 256));
 		if (c->k.gc_prof) { unsigned long long one = 1; CK(mga_h2d_s(sc, (char*)P->gcctl.p + 15 * 8, &one, 8)); CK(mga_ssync(sc)); }
 		CK(gchain_launch(c, c->in.n, 0, 0, (int32_t*)P->gcretry.p));
-		CK(mga_d2h_s(sc, ctl, P->gcctl.p, 72)); CK(mga_ssync(sc));
+		CK(mga_d2h_s(sc, ctl, P->gcctl.p, 88)); CK(mga_ssync(sc));
 		if ((int64_t)ctl[1] <= c->gc_cap && (int64_t)ctl[2] <= c->lc_cap && (int64_t)ctl[6] <= c->ga_cap) break;
 		/* a record pool was too small: size it to what the kernel asked for and run the chunk again */
 		if (attempt >= 2) { mga_set_error("graph chaining: record pools keep overflowing (%lld/%lld/%lld)", (long long)ctl[1], (long long)ctl[2], (long long)ctl[6]); return -1; }
@@ -479,6 +479,7 @@ static int gchain_run(chunk_t *c)
 		if ((int64_t)ctl[2] > c->lc_cap) c->lc_cap = (int64_t)ctl[2] * 2;
 		if ((int64_t)ctl[6] > c->ga_cap) c->ga_cap = (int64_t)ctl[6] * 2;
 	}
+	mga_gc_wg_count((int64_t)ctl[9], (int64_t)ctl[10]);
 	if ((int64_t)ctl[3] > 0) CK(gchain_retry(c, (int64_t)ctl[3]));
 	return 0;
 }

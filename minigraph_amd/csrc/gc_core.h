@@ -2276,6 +2276,13 @@ typedef struct {
 	int32_t ed, n_mid, n_gwfa, n_shortk, n_fast;
 	int64_t mid_off;              /* the walk's inner vertices: mid_pool[mid_off .. mid_off + n_mid) */
 } gc_job_t;
+#define GC_JOB_TAKEN (-1)  /* gc_job_t.read of a job the workgroup form has served (k_gwfa_wg.hip): k_gchain_p2 passes it by */
+#define GC_JOB_N_CLASS 8
+GC_HD int gc_job_class(const gc_job_t *q) /* by the query gap of the bridge, longest first (the gap is what is known beforehand of a bridge's cost) */
+{
+	const int32_t ql = (q->c1->qs + q->span) - (q->c0->qe - q->span);
+	return ql >= 1600 ? 0 : ql >= 1100 ? 1 : ql >= 800 ? 2 : ql >= 600 ? 3 : ql >= 450 ? 4 : ql >= 300 ? 5 : ql >= 150 ? 6 : 7;
+}
 
 GC_HD int gc_asm_kept(const gc_par_t *P, const uint64_t *u, const gc_chain_t *c, int32_t i, int32_t st)
 {

@@ -207,6 +207,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GC_AB_W
 //   k_gchain_p2  a wavefront per bridge, longest query gaps first: gc_job_run in a scratch arena, the walk's inner vertices into the chunk's vertex pool;
 //   k_gchain_p3  a wavefront per read of the state pool: the assembly's second half consuming the bridges in order, measuring, ordering, parents, filters
 //                (gc_read_p3), records published to the chunk's pools exactly as k_gchain does.
+// With MGA_GC_BRIDGE_WG=1 a FOURTH launch sits between parts 1 and 2: k_gwfa_wg_jobs (k_gwfa_wg.hip) runs the bridges over the longest query gaps on a workgroup of 8 wavefronts
+// each, their wavefronts of cells in LDS; a bridge it cannot hold is left untouched and part 2 takes it as before.
 // Nothing is read across a launch boundary that was not written by a block copy at the end of the previous launch's turn (the pattern k_gchain -> k_plan already
 // relies on); every wavefront works in its own scratch arena, as in the one-kernel form.  A read that runs out of arena / pool room in any part goes to the retry
 // list and is redone by k_gchain in a large arena.
@@ -221,10 +223,15 @@ struct gck_split_t {
 	int64_t *p3list;                           // offsets of the states, in the order part 1 finished them
 	gc_job_t *jobs; int64_t jobs_cap;
 	int32_t *mid; int64_t mid_cap;             // inner vertices of the bridges' walks
-	unsigned long long *sctl;                  // [0] state bytes used, [1] jobs listed, [2] vertices used, [3] states listed, [4] next state of part 3, [8..15] next job of part 2 per length class
+	unsigned long long *sctl;                  // [0] state bytes used, [1] jobs listed, [2] vertices used, [3] states listed, [4] next state of part 3, [5] next job of the workgroup form, [8..15] next job of part 2 per length class
 };
+#define GC_BRIDGE_WG_CLASSES 4   /* MGA_GC_BRIDGE_WG: bridges over a query gap of at least 600 bases (classes 0-3 of gc_job_class) go to the workgroup form.  [measured, profiles/gc_bridge_wg_bench.txt]
+                                  * on the bench workload the longest bridges of a chunk (18-27 Mcycles on a wavefront) span gaps of 580-980 bases and no gap reaches 1 100, where the
+                                  * constant first stood by argument; their wavefronts hold 300-500 cells, inside the form's 1 024.  With 4 the form serves ~230 bridges per 125 000 reads, 2-3 times faster each, and the
+                                  * bridge launch is still SLOWER (151-159 against 117-124 ms): bridges over shorter gaps run as long, so part 2's tail stays and this launch adds its own */
+#define GC_BRIDGE_WG_GROUPS 256  /* its persistent workgroups: one per CU */
 #define GCS_A16(x) (((int64_t)(x) + 15) & ~(int64_t)15)
-#define GCS_N_CLASS 8
+#define GCS_N_CLASS GC_JOB_N_CLASS
 struct gcs_view_t { gcs_hdr_t *h; mg128_t *a; gc_chain_t *c; uint64_t *u2; int32_t *kept; gc_rec_t *gc; int64_t bytes; };
 // where the arrays of a block with these counts lie (one definition for the writer, the readers and the host's emulation of the hand-over)
 __host__ __device__ inline void gcs_view(char *blk, int32_t n_b, int32_t n_c, int32_t n_u2, int32_t n_gc, gcs_view_t *v)
@@ -272,11 +279,7 @@ __host__ __device__ inline void gcs_setup_p3(char *blk, mg128_t *res_a, gc_read_
 	R->n_gc = h->n_gc, R->n_lc = R->n_a = 0, R->gc = v.gc, R->lc = 0, R->a = res_a, R->n_gwfa = R->n_fast = 0, R->n_shortk = h->n_shortk;
 	sp->c = v.c, sp->u2 = v.u2, sp->kept = v.kept, sp->n_c = h->n_c, sp->n_u2 = h->n_u2, sp->n_jobs = h->n_jobs, sp->done = 0;
 }
-__device__ __forceinline__ int gcs_job_class(const gc_job_t *q) // by the query gap of the bridge, longest first (the gap is what is known beforehand of a bridge's cost)
-{
-	const int32_t ql = (q->c1->qs + q->span) - (q->c0->qe - q->span);
-	return ql >= 1600 ? 0 : ql >= 1100 ? 1 : ql >= 800 ? 2 : ql >= 600 ? 3 : ql >= 450 ? 4 : ql >= 300 ? 5 : ql >= 150 ? 6 : 7;
-}
+__device__ __forceinline__ int gcs_job_class(const gc_job_t *q) { return gc_job_class(q); } // by the query gap of the bridge, longest first (gc_core.h)
 
 // A value every lane holds alike, as a SCALAR: branches on it are scalar branches.  The persistent loops below fetch their work with one lane's atomic; when the fetched index
 // stayed a per-lane value (__shfl), the compiler treated every `continue` / `break` of the loop as divergent and restructured it into nested exec-mask loops -- [measured, round 4]
@@ -407,7 +410,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GC_AB_P
 			if (lane == 0) base = (long long)atomicAdd(&S.sctl[8 + cls], (unsigned long long)quantum);
 			base = gck_uni64(base);
 			if (base >= n_jobs) break;
-			uint64_t todo = __ballot(lane < quantum && base + lane < n_jobs && gcs_job_class(&S.jobs[base + lane]) == cls && (only_job < 0 || base + lane == only_job));
+			uint64_t todo = __ballot(lane < quantum && base + lane < n_jobs && gcs_job_class(&S.jobs[base + lane]) == cls && S.jobs[base + lane].read != GC_JOB_TAKEN && (only_job < 0 || base + lane == only_job));
 			while (todo) {
 				gc_job_t *q = &S.jobs[base + (__ffsll((long long)todo) - 1)];
 				todo &= todo - 1;
@@ -557,6 +560,12 @@ extern "C" int mga_dev_gchain(mga_sctx_t *sc, const mga_didx_t *ix, const mg_map
 		mga_prof_end(sc->stream, MGA_K_GCHAIN);
 		GCS_DBG("part 1");
 		mga_prof_begin(sc->stream, MGA_K_GCHAIN2);
+		// MGA_GC_BRIDGE_WG=1: the bridges of the top GC_BRIDGE_WG_CLASSES gap classes get a workgroup each (k_gwfa_wg.hip), in a launch of their own in front of part 2, which then
+		// takes the rest and whatever that launch handed back (counted with part 2's time)
+		if (getenv("MGA_GC_BRIDGE_WG") && atoi(getenv("MGA_GC_BRIDGE_WG")) > 0) {
+			int groups = (int)((size_t)wmax < (size_t)GC_BRIDGE_WG_GROUPS ? wmax : GC_BRIDGE_WG_GROUPS);
+			if (mga_dev_gwfa_wg_jobs(sc, S.jobs, S.jobs_cap, S.mid, S.mid_cap, S.sctl, GC_BRIDGE_WG_CLASSES, &G, &P, (char*)arena->p, (int64_t)ab, groups, d_ctl) < 0) return -1;
+		}
 		hipLaunchKernelGGL(k_gchain_p2, dim3(waves2), dim3(64), 0, (hipStream_t)sc->stream, S, G, P, (char*)arena->p, (int64_t)ab, d_ctl, -1LL);
 		mga_prof_end(sc->stream, MGA_K_GCHAIN2);
 		GCS_DBG("part 2");
@@ -574,7 +583,12 @@ extern "C" int mga_dev_gchain(mga_sctx_t *sc, const mga_didx_t *ix, const mg_map
 							mx * 1e-6, (hc[1].qs + hj[imx].span) - (hc[0].qe - hj[imx].span), hj[imx].ed, hj[imx].n_mid, hj[imx].n_shortk);
 					for (int b_ = 0; b_ < 12; ++b_) fprintf(stderr, " %zu", hist[b_]);
 					fprintf(stderr, "\n");
-					{ // the longest bridge once more, ALONE on the device, with per-stage cycle sums and counts
+					{ // (MGA_GC_BRIDGE_WG=1) what the workgroup form served, with the durations it left in n_fast
+						size_t n_wg_ = 0; long long mx_wg_ = 0, mx_p2_ = 0;
+						for (size_t i_ = 0; i_ < nj; ++i_) { const long long t_ = (long long)hj[i_].n_fast << 10; if (hj[i_].read == GC_JOB_TAKEN) { ++n_wg_; if (t_ > mx_wg_) mx_wg_ = t_; } else if (t_ > mx_p2_) mx_p2_ = t_; }
+						if (n_wg_) fprintf(stderr, "[gc-split] part 2: %zu of the bridges served by the workgroup form, its longest %.2f Mcycles; the longest one on a wavefront %.2f Mcycles\n", n_wg_, mx_wg_ * 1e-6, mx_p2_ * 1e-6);
+					}
+					if (hj[imx].read != GC_JOB_TAKEN) { // the longest bridge once more, ALONE on the device, with per-stage cycle sums and counts (part 2 passes by a bridge the workgroup form served)
 						unsigned long long z_[32], one_ = 1, tk_[16];
 						memset(z_, 0, sizeof z_);
 						(void)hipMemcpy(sb + 64, z_, 64, hipMemcpyHostToDevice);          // job counters of the classes

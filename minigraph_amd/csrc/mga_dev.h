@@ -266,6 +266,18 @@ int mga_dev_gchain(mga_sctx_t *sc, const mga_didx_t *ix, const mg_mapopt_t *opt,
 				   const int64_t *d_mini_off, const int32_t *d_mini, const int64_t *d_q_off, const char *d_seq, const uint32_t *d_hash, const int32_t *d_rflag,
 				   mga_gc_hdr_t *d_hdr, void *d_gc_pool, int64_t gc_cap, mg_llchain_t *d_lc_pool, int64_t lc_cap, mg128_t *d_a_pool, int64_t a_cap,
 				   unsigned long long *d_ctl, int32_t *d_retry);
+/* ---- ONE bridge (GWFA call) on a workgroup of 8 wavefronts (k_gwfa_wg.hip) ----
+ * mga_dev_gwfa_wg_jobs: the launch of the mapping path (MGA_GC_BRIDGE_WG=1) over the chunk's job array, in front of k_gchain_p2: jobs of a gap class below n_cls; G / P: the
+ * launcher's gc_graph_t / gc_par_t; arena: n_groups blocks of arena_bytes; sctl: the split form's counters ([1] jobs listed, [2] walk vertices used, [5] next job of this
+ * launch); d_ctl[9] / [10] count the jobs served / handed back.
+ * mga_dev_gwfa_stage: the listed problems in one launch, form 0 a wavefront each (status_ok: what a served problem reports), form 1 a workgroup each; d_out = int32[4] per
+ * problem { ed, n_path, status, peak }, walks at d_path + i * path_cap; *d_counter = 0 on entry. */
+int mga_dev_gwfa_wg_jobs(mga_sctx_t *sc, void *jobs, int64_t jobs_cap, int32_t *mid, int64_t mid_cap, unsigned long long *sctl, int n_cls, const void *G, const void *P,
+						 char *arena, int64_t arena_bytes, int n_groups, unsigned long long *d_ctl);
+int mga_dev_gwfa_stage(mga_sctx_t *sc, const mga_didx_t *ix, int form, int n_list, const int32_t *d_list, const mga_gwfa_prob_t *d_prob, const char *d_qseq, char *d_arena,
+					   int64_t arena_bytes, int n_groups, int32_t path_cap, int32_t status_ok, int32_t *d_out, int32_t *d_path, unsigned long long *d_counter);
+void mga_dev_gwfa_wg_shape(int *nw, int *cells);
+void mga_gc_wg_count(int64_t served, int64_t back); /* rqphase.c: the counters behind mga_gc_wg_stats */
 /* flat records of one read -> a malloc'ed mg_gchains_t (div and MAPQ computed here, on the host's libm) */
 mg_gchains_t *mga_gchains_from_flat(int32_t n_gc, const void *gc_recs, int32_t n_lc, const mg_llchain_t *lc, int32_t n_a, const mg128_t *a,
 									int32_t rep_len, int32_t qlen, int32_t n_mz, int32_t min_gc_score);

@@ -115,6 +115,11 @@ static void rq_fwd_worker(void *data, int64_t j, int tid)
 static int64_t g_rq_dev_stat[8];
 void mga_rq_dev_stats(int64_t *out, int reset) { int k; for (k = 0; k < 8; ++k) { out[k] = __atomic_load_n(&g_rq_dev_stat[k], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_rq_dev_stat[k], 0, __ATOMIC_RELAXED); } }
 
+/* bridges of graph chaining that the workgroup form (k_gwfa_wg.hip, MGA_GC_BRIDGE_WG=1) [0] served, [1] handed back to k_gchain_p2, summed over the chunks */
+static int64_t g_gc_wg_stat[2];
+void mga_gc_wg_count(int64_t served, int64_t back) { if (served) __atomic_fetch_add(&g_gc_wg_stat[0], served, __ATOMIC_RELAXED); if (back) __atomic_fetch_add(&g_gc_wg_stat[1], back, __ATOMIC_RELAXED); }
+void mga_gc_wg_stats(int64_t *out, int reset) { int k; for (k = 0; k < 2; ++k) { out[k] = __atomic_load_n(&g_gc_wg_stat[k], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_gc_wg_stat[k], 0, __ATOMIC_RELAXED); } }
+
 typedef struct { int64_t len; int32_t k; } rq_ord_t;
 static int rq_ord_cmp(const void *x, const void *y) { const rq_ord_t *p = (const rq_ord_t*)x, *q = (const rq_ord_t*)y; return p->len > q->len ? -1 : p->len < q->len ? 1 : (p->k > q->k) - (p->k < q->k); }
 
