@@ -437,21 +437,35 @@ void mga_rq_dev_stats(int64_t *out, int reset);
  * every problem a wavefront (the routine of k_gchain_p2), MGA_GWFA_FORM_WG a workgroup of 8 wavefronts with the wavefronts of cells in LDS (k_gwfa_wg.hip) -- a problem
  * that form cannot hold (more than 1 024 cells in a wavefront, ...) comes back and is redone by the wave form.  Out, per problem: ed[i], n_path[i], the walk at
  * path + i * path_cap, status[i] (which form served it), peak[i] (largest wavefront of cells the workgroup form saw; 0 in the wave form).
+ * MGA_GWFA_FORM_WGX is the wide workgroup form (k_gwfa_wgx.hip): wavefronts of up to 3 072 cells, 20 bytes a cell, in two LDS buffers and a third in the job's arena, the
+ * flagged cells of a dedup sorted on all 8 wavefronts; the problems are taken longest query first by one workgroup per compute unit.  It serves the bridges of long,
+ * diverged gaps that MGA_GWFA_FORM_WG hands back for their width; what it hands back itself (status MGA_GWFA_BACK) is redone by the wave form.
  * Environment of the mapping path: MGA_GC_BRIDGE_WG=1 (with MGA_GC_SPLIT=1) sends the bridges over query gaps of at least 600 bases to the workgroup form in a launch of their
  * own in front of k_gchain_p2; unset or 0: as before.  mga_gc_wg_stats: out[0] bridges that form served, out[1] bridges it handed back, since the last reset. */
 typedef struct { int64_t q_off; int32_t ql; uint32_t v0; int32_t off0; uint32_t v1; int32_t off1, max_lag, s_term, pad; } mga_gwfa_prob_t;
 #define MGA_GWFA_FORM_WAVE 0
 #define MGA_GWFA_FORM_WG   1
+#define MGA_GWFA_FORM_WGX  2
 #define MGA_GWFA_WG     0   /* status: served by the workgroup form */
 #define MGA_GWFA_BACK   1   /* handed back by the workgroup form, served by the wave form */
 #define MGA_GWFA_WAVE   2   /* served by the wave form, as asked */
 #define MGA_GWFA_E_ROOM 3   /* not served: the walk is longer than path_cap, or the scratch arena was too small (ed = -1, no walk) */
+#define MGA_GWFA_WGX    4   /* served by the wide workgroup form */
 int32_t mga_gwfa_bridge(const gfa_t *g, const gfa_edseq_t *es, int32_t ql, const char *q, uint32_t v0, int32_t off0, uint32_t v1, int32_t off1,
 						int32_t max_lag, int32_t s_term, int32_t **path, int32_t *nv);
 int mga_gwfa_bridge_batch(const mg_idx_t *gi, int n, const char *qseq, int64_t n_q, const mga_gwfa_prob_t *prob, int form, int32_t path_cap,
 						  int32_t *ed, int32_t *n_path, int32_t *path, int32_t *status, int32_t *peak);
 void mga_gwfa_wg_shape(int *nw, int *cells); /* wavefronts of the workgroup form, cells its wavefront buffers hold */
+void mga_gwfa_wgx_shape(int *nw, int *cells_cur, int *cells_wide); /* the wide form: wavefronts, cells of the wavefront it consumes, cells of the one it produces (before the dedup) */
 void mga_gc_wg_stats(int64_t *out, int reset);
+/* of this thread's last mga_gwfa_bridge call: out[0] the largest wavefront of cells after a dedup, out[1] the cells the pruning dropped (above 1 000 cells, every 16th step) */
+void mga_gwfa_bridge_cells(int32_t out[2]);
+/* of the wide form's calls since the last reset: out[0] the most flagged cells one dedup sorted on its 8 wavefronts, out[1] the steps it replayed with gc_ksort */
+void mga_gwfa_wgx_stats(int64_t out[2], int reset);
+/* -x asm: MGA_ASM_DEV_BRIDGE=1 takes the bridges of a batch's contigs off the host threads -- part 1 of the graph chaining per contig, one mga_gwfa_bridge_batch call in the
+ * wide form for all of them, part 3 per contig; unset or 0: every contig whole on a host thread, as before (=2 is NOT a supported setting: the seam of the CPU tests, the same route with
+ * mga_gwfa_bridge in place of the device call, one bridge after another).  out[0] bridges the wide form served, out[1] served by the wave form after a hand-back, out[2] made on the host. */
+void mga_asm_bridge_stats(int64_t out[3], int reset);
 int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lchain_par_t *par,
 					 uint64_t **u, int64_t **u_off, mg128_t **b, int64_t **b_off);
 /* radix_sort_128x (ksort.h:112-162 through misc.c:9) as the chaining kernels run it: array i = a[a_off[i]..a_off[i+1]) is sorted in place by x with the

@@ -356,7 +356,7 @@ def lcdp_fwd_batch(a, items, max_dist_y=5000, bw=500, max_skip=25, max_iter=5000
 
 gwfa_prob_dtype = np.dtype([("q_off", "<i8"), ("ql", "<i4"), ("v0", "<u4"), ("off0", "<i4"), ("v1", "<u4"), ("off1", "<i4"), ("max_lag", "<i4"), ("s_term", "<i4"),
                             ("pad", "<i4")])   # mga_gwfa_prob_t
-GWFA_STATUS = {0: "workgroup", 1: "handed back", 2: "wave", 3: "no room"}
+GWFA_STATUS = {0: "workgroup", 1: "handed back", 2: "wave", 3: "no room", 4: "wide workgroup"}
 
 
 def gwfa_wg_shape():
@@ -366,10 +366,17 @@ def gwfa_wg_shape():
     return nw.value, cells.value
 
 
+def gwfa_wgx_shape():
+    """(wavefronts per workgroup, cells of the wavefront it consumes, cells of the one it produces) of the wide workgroup form of the bridge (k_gwfa_wgx.hip)"""
+    nw, cur, wide = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().mga_gwfa_wgx_shape(C.byref(nw), C.byref(cur), C.byref(wide))
+    return nw.value, cur.value, wide.value
+
+
 def gwfa_bridge_batch(graph, problems, form="workgroup", path_cap=4096):
     """the bridge between two linear chains (graph wavefront alignment) for n problems (query bytes, v0, off0, v1, off1, max_lag, s_term) on the device against the
     graph's replica; form "wave": a wavefront per problem, "workgroup": 8 wavefronts per problem with the cells in LDS, what that form cannot hold going through the
-    wave form -> list of (ed, path vertices, status, peak): ed -1 = not reached, status a key of GWFA_STATUS, peak = largest wavefront of cells (workgroup form)"""
+    wave form, "wide": the workgroup form for wavefronts of up to 3 072 cells (same hand-back) -> list of (ed, path vertices, status, peak): ed -1 = not reached, status a key of GWFA_STATUS, peak = largest wavefront of cells (workgroup form)"""
     L = load()
     n = len(problems)
     qseq, q_off = concat([p[0] for p in problems])
@@ -380,7 +387,7 @@ def gwfa_bridge_batch(graph, problems, form="workgroup", path_cap=4096):
     path = np.zeros((max(n, 1), path_cap), dtype=np.int32)
     L.mga_gwfa_bridge_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_int, C.c_int32] + [C.c_void_p] * 5
     L.mga_gwfa_bridge_batch.restype = C.c_int
-    _check(L.mga_gwfa_bridge_batch(graph.gi, n, qseq, len(qseq), prob.ctypes.data, {"wave": 0, "workgroup": 1}[form], path_cap,
+    _check(L.mga_gwfa_bridge_batch(graph.gi, n, qseq, len(qseq), prob.ctypes.data, {"wave": 0, "workgroup": 1, "wide": 2}[form], path_cap,
                                    ed.ctypes.data, n_path.ctypes.data, path.ctypes.data, status.ctypes.data, peak.ctypes.data), "mga_gwfa_bridge_batch")
     return [(int(ed[i]), [int(x) for x in path[i, :n_path[i]]], int(status[i]), int(peak[i])) for i in range(n)]
 
@@ -390,6 +397,27 @@ def gc_wg_stats(reset=False):
     st = (C.c_int64 * 2)()
     load().mga_gc_wg_stats(st, 1 if reset else 0)
     return {"served": st[0], "handed_back": st[1]}
+
+
+def asm_bridge_stats(reset=False):
+    """bridges of -x asm contigs under MGA_ASM_DEV_BRIDGE since the last reset: served by the wide workgroup form / by the wave form after a hand-back / made on the host"""
+    st = (C.c_int64 * 3)()
+    load().mga_asm_bridge_stats(st, 1 if reset else 0)
+    return {"wide": st[0], "handed_back": st[1], "host": st[2]}
+
+
+def gwfa_wgx_stats(reset=False):
+    """the wide form's calls since the last reset: the most flagged cells one dedup sorted on its 8 wavefronts, the steps it replayed with gc_ksort"""
+    st = (C.c_int64 * 2)()
+    load().mga_gwfa_wgx_stats(st, 1 if reset else 0)
+    return {"max_flagged": st[0], "replayed": st[1]}
+
+
+def gwfa_bridge_cells():
+    """of this thread's last mga_gwfa_bridge call: (largest wavefront of cells after a dedup, cells the pruning dropped)"""
+    st = (C.c_int32 * 2)()
+    load().mga_gwfa_bridge_cells(st)
+    return st[0], st[1]
 
 
 def gaf_div_batch(div):

@@ -134,6 +134,17 @@ static void chain_worker(void *data, int64_t i, int tid)
 	mg_gchains_t *gcs;
 
 	int64_t tc = cpu_now();
+	if (b->asm_phase == 3) { /* the contig's bridges are answered: the rest of its graph chaining, then the gap list as in one pass */
+		struct asm_read_s *r = &b->asmb[i];
+		if (r->sp == 0) return;
+		gcs = mga_gchain_split_p3(r->sp, b->asm_ed + r->job0, b->asm_np + r->job0, b->asm_path + r->job0 * b->asm_path_cap, b->asm_path_cap, b->asm_st ? b->asm_st + r->job0 : 0,b->rep_len[i], b->n_mz[i]);
+		free(r->u); free(r->a);
+		r->sp = 0;
+		if (gcs == 0) return; /* the device call failed: the contig's state is released, the chunk fails in mga_batch_chain() */
+		CPU_ADD(C_GCGEN, tc);
+		b->gcs[i] = gcs;
+		goto plan;
+	}
 	b->gcs[i] = 0;
 	if (qlen == 0) return; /* map-algo.c:359-360 */
 	if (opt->max_qlen > 0 && qlen > opt->max_qlen) return;
@@ -181,6 +192,13 @@ do_rescue:;
 		const int32_t n_mini = (int32_t)(b->mini_off[i + 1] - b->mini_off[i]);
 		int64_t n_anchor = 0;
 		for (k = 0; k < n_lc; ++k) n_anchor += (int32_t)u[k];
+		if (b->asm_phase == 1) { /* up to the list of bridges; u and a stay with the contig until its second visit */
+			struct asm_read_s *r = &b->asmb[i];
+			r->sp = mga_gchain_split_p1(gi, b->seg_len, opt, b->pen_gap, qlen, hash, n_lc, u, a, (int32_t)n_anchor, n_mini, mini, seq, &r->n_jobs, &r->n_q);
+			r->u = u, r->a = a;
+			CPU_ADD(C_GCGEN, tc);
+			return;
+		}
 		gcs = mga_gchain_host_read(gi, b->seg_len, opt, b->pen_gap, qlen, hash, n_lc, u, a, (int32_t)n_anchor, n_mini, mini, seq, b->rep_len[i], b->n_mz[i], 0, 0);
 	}
 	free(u); u = 0;
@@ -241,6 +259,51 @@ plan:
 	}
 }
 
+/* -x asm with MGA_ASM_DEV_BRIDGE: the contigs' bridges leave the host threads.  chain_worker runs every contig up to its list of bridges, the lists are gathered in
+ * (contig, bridge) order with their stretches of query, ONE call of the wide workgroup form (k_gwfa_wgx.hip) answers them all, and chain_worker takes each contig up again.
+ * The call goes through the stage context, which chunks share: one at a time.  A failed device call fails the chunk. */
+static int asm_bridge_mode(void)
+{
+	static int mode = -1;
+	if (mode < 0) { const char *e = getenv("MGA_ASM_DEV_BRIDGE"); mode = e ? atoi(e) : 0; if (mode < 0 || mode > 2) mode = 0; }
+	return mode;
+}
+static int asm_bridge_chain(mga_batch_t *b)
+{
+	static pthread_mutex_t mtx = PTHREAD_MUTEX_INITIALIZER;
+	const int32_t path_cap = 512; /* vertices of a walk; a longer one comes back MGA_GWFA_E_ROOM and its bridge is made on the contig's thread */
+	int64_t i, n_jobs = 0, n_q = 0;
+	int rc = 0;
+	b->asmb = MGA_CALLOC(struct asm_read_s, b->n > 0 ? b->n : 1);
+	b->asm_phase = 1, b->asm_path_cap = path_cap;
+	mga_parallel_for(b->n_threads, b->n, chain_worker, b);
+	for (i = 0; i < b->n; ++i) b->asmb[i].job0 = n_jobs, n_jobs += b->asmb[i].n_jobs, n_q += b->asmb[i].n_q;
+	mga_gwfa_prob_t *prob = MGA_MALLOC(mga_gwfa_prob_t, n_jobs + 1);
+	char *qbuf = MGA_MALLOC(char, n_q + 1);
+	int32_t *ed = MGA_MALLOC(int32_t, n_jobs * 4 + 4), *np = ed + n_jobs, *st = np + n_jobs, *peak = st + n_jobs, *path = MGA_MALLOC(int32_t, n_jobs * path_cap + 1);
+	for (i = 0, n_q = 0; i < b->n; n_q += b->asmb[i].n_q, ++i)
+		if (b->asmb[i].sp) mga_gchain_split_probs(b->asmb[i].sp, prob + b->asmb[i].job0, qbuf, n_q);
+	if (n_jobs >= INT32_MAX) mga_set_error("asm bridges: %ld problems in one batch", (long)n_jobs), rc = -1;
+	else if (asm_bridge_mode() == 1) {
+		pthread_mutex_lock(&mtx);
+		rc = mga_gwfa_bridge_batch(b->gi, (int)n_jobs, qbuf, n_q, prob, MGA_GWFA_FORM_WGX, path_cap, ed, np, path, st, peak);
+		pthread_mutex_unlock(&mtx);
+	} else for (i = 0; i < n_jobs; ++i) { /* (tests, no device) the host routine behind the same records */
+		int32_t *w = 0, nv = 0;
+		const mga_gwfa_prob_t *p = &prob[i];
+		ed[i] = mga_gwfa_bridge(b->gi->g, b->gi->es, p->ql, qbuf + p->q_off, p->v0, p->off0, p->v1, p->off1, p->max_lag, p->s_term, &w, &nv);
+		st[i] = nv <= path_cap ? MGA_GWFA_WAVE : MGA_GWFA_E_ROOM, np[i] = nv <= path_cap ? nv : 0;
+		if (nv > 0 && nv <= path_cap) memcpy(path + i * path_cap, w, (size_t)nv * 4);
+		free(w);
+	}
+	/* a failed call leaves no answers: the second visit then only releases what the first one built (asm_st == NULL), and the chunk fails */
+	b->asm_ed = ed, b->asm_np = np, b->asm_st = rc < 0 ? 0 : st, b->asm_path = path, b->asm_phase = 3;
+	mga_parallel_for(b->n_threads, b->n, chain_worker, b);
+	b->asm_phase = 0;
+	free(prob); free(qbuf); free(ed); free(path); free(b->asmb); b->asmb = 0;
+	return rc;
+}
+
 int mga_batch_chain(mga_batch_t *b, const int32_t *n_mz, const int32_t *rep_len, const int32_t *mini_pos, const int64_t *mini_off,
 					const int32_t *nu, const int32_t *nb, const uint64_t *u, const mg128_t *a, const int64_t *a_off, int a_is_raw, const int32_t *rescue_flag)
 {
@@ -250,7 +313,11 @@ int mga_batch_chain(mga_batch_t *b, const int32_t *n_mz, const int32_t *rep_len,
 	b->n_mz = n_mz, b->rep_len = rep_len, b->mini_pos = mini_pos, b->mini_off = mini_off;
 	b->nu = nu, b->nb = nb, b->u = u, b->a = a, b->a_off = a_off, b->a_is_raw = a_is_raw;
 	if (a_is_raw) rq_chain_all(b);
-	mga_parallel_for(b->n_threads, b->n, chain_worker, b);
+	b->asm_phase = 0;
+	int asm_rc = 0;
+	if (a_is_raw && b->gc_hdr == 0 && asm_bridge_mode() != 0) {
+		asm_rc = asm_bridge_chain(b);
+	} else mga_parallel_for(b->n_threads, b->n, chain_worker, b);
 	if (b->rq) { free(b->rq); b->rq = 0; }
 	for (t = 0; t < b->n_threads; ++t) {
 		b->tp_prob_base[t + 1] = b->tp_prob_base[t] + b->tp[t].n_prob;
@@ -259,6 +326,7 @@ int mga_batch_chain(mga_batch_t *b, const int32_t *n_mz, const int32_t *rep_len,
 		b->tp_chain_base[t + 1] = b->tp_chain_base[t] + b->tp[t].n_chain;
 		b->tp_vert_base[t + 1] = b->tp_vert_base[t] + b->tp[t].n_vert;
 	}
+	if (asm_rc < 0) return asm_rc; /* (the message is mga_gwfa_bridge_batch's) */
 	if (b->rq_dev_err) { mga_set_error("RMQ forward pass on the device failed: %s", b->rq_dev_errmsg); return -1; } /* fail loudly: a device error must not pass for a slow job */
 	return 0;
 }

@@ -48,6 +48,10 @@ struct mga_batch_s {
 	const mg128_t *a;
 	int a_is_raw;
 	struct rq_read_s *rq;   /* a_is_raw: per-read state of the phased RMQ chaining (rqphase.c) */
+	/* MGA_ASM_DEV_BRIDGE: chain_worker runs twice, asm_phase 1 up to the list of bridges (asmb[i].sp), 3 from their answers on; 0: one pass */
+	int asm_phase, asm_path_cap;
+	struct asm_read_s { mga_gcsplit_t *sp; uint64_t *u; mg128_t *a; int32_t n_jobs; int64_t job0, n_q; } *asmb;
+	const int32_t *asm_ed, *asm_np, *asm_path, *asm_st;
 	/* round 5: the forward passes of the RMQ chainer on the device (k_rmq.hip), one read at a time on the chunk's stream; rq_harr = pinned arrays p | f | v | t of ALL the
 	 * chunk's anchors (the device writes f, p, v straight into them), rq_tot = their length in anchors */
 	mga_rq_dev_fwd_f rq_dev_fwd;

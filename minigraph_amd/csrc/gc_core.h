@@ -1112,6 +1112,14 @@ static void gc_stats_dump(void)
 #define GC_STAT(...)
 #endif
 
+/* host only (tests): the largest wavefront of cells the last gc_gwfa() call of this thread held after a dedup, and the cells its prunings dropped */
+#if !defined(__HIP_DEVICE_COMPILE__)
+static __thread int32_t gc_host_wf_peak, gc_host_wf_pruned;
+#define GC_HOST_NOTE(...) __VA_ARGS__
+#else
+#define GC_HOST_NOTE(...)
+#endif
+
 #define GC_DSHIFT 0x40000000
 #define GC_FAST_GAP 400 /* longest query gap whose GWFA call tries the LDS scratch first */
 /* 32 bytes, 16-byte aligned: a cell is moved as two aligned 16-byte words.  (24 bytes at 8-byte alignment let the compiler fuse a copy into a 16-byte access at
@@ -2007,7 +2015,9 @@ GC_HD int gc_gw_step(gc_arena_t *A, gc_gw_t *z, uint32_t v1, int32_t off1, int *
 		GC_TRY(gc_gw_dedup(A, z, &B->n, B->a));
 	}
 	GC_TICK(A, 14);
+	GC_HOST_NOTE(if (B->n > gc_host_wf_peak) gc_host_wf_peak = B->n; const int32_t n_before_ = B->n;)
 	if (z->max_lag > 0 && B->n > z->max_chk && ((z->s + 1) & 0xf) == 0) B->n = gc_gw_prune(B->n, B->a, (uint32_t)z->max_lag, z->bw_dyn);
+	GC_HOST_NOTE(gc_host_wf_pruned += n_before_ - B->n;)
 	z->cur ^= 1;
 	return GC_OK;
 }
@@ -2019,6 +2029,7 @@ GC_HDN int gc_gwfa(gc_arena_t *A, const gc_graph_t *G, int32_t ql, const char *q
 	GC_STATE(gc_gw_t, z);
 	memset(&z, 0, sizeof z);
 	*ed = -1, *path = 0, *n_path = 0;
+	GC_HOST_NOTE(gc_host_wf_peak = gc_host_wf_pruned = 0;)
 	z.G = G, z.ql = ql, z.q = q;
 	z.max_chk = 1000, z.bw_dyn = 1000, z.max_lag = max_lag, z.i_term = 500000000LL; /* gchain1.c:361-363 */
 	GC_TRY(gc_vec_reserve(A, z.wf[0], 16));

@@ -769,6 +769,117 @@ extern "C" mg_gchains_t *mga_gchain_host_read(const mg_idx_t *gi, const int32_t 
 	return gs;
 }
 
+// ---- a contig's graph chaining in two host calls with its bridges in between (-x asm, MGA_ASM_DEV_BRIDGE: batch.c) ----
+// part 1 (gc_read_p1) on a host thread leaves its state in an object of the contig's own -- arena, chain records, the list of bridges --; mga_gchain_split_probs() writes the
+// bridges as the GWFA problems gc_bridge_walk() would pose (the same ten arguments of gc_gwfa), their queries gathered into one buffer; part 3 takes the answers of
+// mga_gwfa_bridge_batch() and finishes the contig.  What an answer does not carry is made up HERE, on the contig's thread, from the chain records the job still points to: a
+// bridge the aligner did not reach (ed < 0) gets the shortest walk of the length the DP chose (the second half of gc_bridge_walk), a bridge that was not served
+// (MGA_GWFA_E_ROOM) is run again whole through gc_job_run.  resolve_overlap has run in part 1 (gc_assemble_begin), so the records the problems are read from are final.
+struct mga_gcsplit_s {
+	gc_arena_t A; gc_graph_t G; gc_par_t P; gc_read_t rd; gc_result_t R; gc_split_t sp;
+	char *mem; gc_job_t *jobs; int rc, n_a, min_gc_score;
+};
+static int64_t g_asm_bridge[3]; // bridges served wide / by the wave form after a hand-back / made on the host
+extern "C" void mga_asm_bridge_stats(int64_t out[3], int reset)
+{
+	for (int i = 0; i < 3; ++i) { out[i] = __atomic_load_n(&g_asm_bridge[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_asm_bridge[i], 0, __ATOMIC_RELAXED); }
+}
+extern "C" mga_gcsplit_t *mga_gchain_split_p1(const mg_idx_t *gi, const int32_t *seg_len, const mg_mapopt_t *opt, float pen_gap, int32_t qlen, uint32_t hash, int32_t n_u, const uint64_t *u,
+											  mg128_t *a, int32_t n_a, int32_t n_mini, const int32_t *mini_pos, const char *qseq, int32_t *n_jobs, int64_t *n_q)
+{
+	mga_gcsplit_t *s = (mga_gcsplit_t*)calloc(1, sizeof *s);
+	const int64_t first = (int64_t)1 << 22;
+	s->mem = (char*)malloc((size_t)first);
+	gc_arena_init(&s->A, s->mem, first, 1);
+	s->G.arc = (const gc_arc_t*)gi->g->arc, s->G.idx = gi->g->idx, s->G.seg_len = seg_len, s->G.es = gi->es;
+	gc_par_from_opt(opt, gi->k, pen_gap, &s->P);
+	s->rd.qlen = qlen, s->rd.hash = hash, s->rd.n_u = n_u, s->rd.u = u, s->rd.a = a, s->rd.n_mini = n_mini, s->rd.mini_pos = mini_pos, s->rd.qseq = qseq;
+	s->n_a = n_a, s->min_gc_score = opt->min_gc_score;
+	s->R.a = (mg128_t*)malloc((size_t)(n_a > 0 ? n_a : 1) * sizeof(mg128_t));
+	s->rc = gc_read_p1(&s->A, &s->G, &s->P, &s->rd, &s->R, &s->sp);
+	*n_jobs = 0, *n_q = 0;
+	if (s->rc == GC_OK && !s->sp.done && s->sp.n_jobs > 0) {
+		s->jobs = (gc_job_t*)calloc((size_t)s->sp.n_jobs, sizeof(gc_job_t));
+		gc_assemble_jobs(s->sp.n_u2, s->sp.u2, s->sp.kept, s->sp.c, 0, GC_ASPAN(a[0]), qseq, s->jobs);
+		*n_jobs = s->sp.n_jobs;
+		for (int32_t k = 0; k < s->sp.n_jobs; ++k) { const gc_job_t *q = &s->jobs[k]; *n_q += (q->c1->qs + q->span) - (q->c0->qe - q->span); }
+	}
+	return s;
+}
+// the contig's bridges as problems prob[0 .. n_jobs), their queries copied to qbuf from q_off on
+extern "C" void mga_gchain_split_probs(const mga_gcsplit_t *s, mga_gwfa_prob_t *prob, char *qbuf, int64_t q_off)
+{
+	for (int32_t k = 0; k < s->sp.n_jobs && s->jobs; ++k) {
+		const gc_job_t *q = &s->jobs[k];
+		const int32_t qs = q->c0->qe - q->span, qe = q->c1->qs + q->span;
+		mga_gwfa_prob_t *p = &prob[k];
+		p->q_off = q_off, p->ql = qe - qs, p->v0 = q->c0->v, p->off0 = q->c0->re - q->span, p->v1 = q->c1->v, p->off1 = q->c1->rs + q->span - 1;
+		p->max_lag = s->P.gdp_max_ed / 2, p->s_term = s->P.gdp_max_ed, p->pad = 0;
+		memcpy(qbuf + q_off, q->qseq + qs, (size_t)(qe - qs));
+		q_off += qe - qs;
+	}
+}
+// the shortest walk of the length the DP chose between the two chains of a bridge the aligner gave up on: gc_bridge_walk's second half (gchain1.c:319-338)
+static int gcs_walk_fallback(gc_arena_t *A, const gc_graph_t *G, gc_job_t *q, std::vector<int32_t> &pool)
+{
+	gc_dst_t dst;
+	gc_walkv_t *w = 0;
+	int32_t n_w = 0;
+	memset(&dst, 0, sizeof dst);
+	dst.v = q->c0->v ^ 1, dst.target_dist = q->c1->dist_pre, dst.target_hash = q->c1->hash_pre, dst.check_hash = 1;
+	const int rc = gc_shortest_k(A, G, q->c1->v ^ 1, 1, &dst, dst.target_dist, MG_MAX_SHORT_K, &w, &n_w);
+	if (rc == GC_E_ARENA) return rc;
+	q->n_shortk = 1, q->ed = -1, q->n_mid = 0, q->mid_off = (int64_t)pool.size();
+	if (rc != GC_OK || n_w == 0 || dst.target_hash != dst.hash) { q->status = GC_JOB_FAILED; return GC_OK; }
+	for (int32_t t = n_w - 2; t >= 1; --t) pool.push_back((int32_t)(w[t].v ^ 1)), ++q->n_mid; /* found backwards: reverse and flip */
+	return GC_OK;
+}
+// ed, n_path, status: the contig's slice of mga_gwfa_bridge_batch's answers, walk k at path + k * path_cap.  Releases s.  status == NULL (the call failed, and the chunk
+// with it): releases s and nothing else, returns NULL.
+extern "C" mg_gchains_t *mga_gchain_split_p3(mga_gcsplit_t *s, const int32_t *ed, const int32_t *n_path, const int32_t *path, int32_t path_cap, const int32_t *status,
+											 int32_t rep_len, int32_t n_mz)
+{
+	int rc = s->rc;
+	if (status == 0) {
+		gc_arena_free_blocks(&s->A);
+		free(s->R.a); free(s->jobs); free(s->mem); free(s);
+		return 0;
+	}
+	if (rc == GC_OK && !s->sp.done) {
+		std::vector<int32_t> pool;
+		int64_t cnt[3] = { 0, 0, 0 };
+		char *m2 = s->jobs ? (char*)malloc(1 << 20) : 0;
+		for (int32_t k = 0; k < s->sp.n_jobs && s->jobs && rc == GC_OK; ++k) {
+			gc_job_t *q = &s->jobs[k];
+			gc_arena_t A2;
+			gc_arena_init(&A2, m2, 1 << 20, 1);
+			if (status[k] == MGA_GWFA_E_ROOM) { // not served: the whole bridge on this thread
+				gc_bres_t b;
+				rc = gc_job_run(&A2, &s->G, &s->P, q, &b);
+				if (rc == GC_OK && q->status == GC_JOB_OK) { q->mid_off = (int64_t)pool.size(); pool.insert(pool.end(), b.mid, b.mid + b.n_mid); }
+				++cnt[2];
+			} else {
+				q->n_gwfa = 1;
+				if (ed[k] >= 0) {
+					q->ed = ed[k], q->n_mid = n_path[k] - 2 > 0 ? n_path[k] - 2 : 0, q->mid_off = (int64_t)pool.size();
+					pool.insert(pool.end(), path + (size_t)k * path_cap + 1, path + (size_t)k * path_cap + 1 + q->n_mid);
+				} else rc = gcs_walk_fallback(&A2, &s->G, q, pool);
+				++cnt[status[k] == MGA_GWFA_WGX ? 0 : status[k] == MGA_GWFA_BACK ? 1 : 2];
+			}
+			gc_arena_free_blocks(&A2);
+		}
+		free(m2);
+		for (int i = 0; i < 3; ++i) __atomic_fetch_add(&g_asm_bridge[i], cnt[i], __ATOMIC_RELAXED);
+		pool.push_back(0);
+		if (rc == GC_OK) rc = gc_read_p3(&s->A, &s->G, &s->P, &s->rd, &s->R, &s->sp, s->jobs, pool.data());
+	}
+	if (rc != GC_OK) s->R.n_gc = s->R.n_lc = s->R.n_a = 0;
+	mg_gchains_t *gs = mga_gchains_from_flat(s->R.n_gc, s->R.gc, s->R.n_lc, s->R.lc, s->R.n_a, s->R.a, rep_len, s->rd.qlen, n_mz, s->min_gc_score);
+	gc_arena_free_blocks(&s->A);
+	free(s->R.a); free(s->jobs); free(s->mem); free(s);
+	return gs;
+}
+
 #if defined(GC_HOST_PROF) && !defined(__HIP_DEVICE_COMPILE__)
 extern "C" void mga_gc_host_prof_dump(void)
 {
@@ -857,6 +968,8 @@ extern "C" int32_t mga_gwfa_bridge(const gfa_t *g, const gfa_edseq_t *es, int32_
 	free(first); free(seg_len);
 	return ed;
 }
+// of this thread's last mga_gwfa_bridge call: out[0] the largest wavefront of cells after a dedup, out[1] the cells the reference's pruning (above 1 000 cells, every 16th step) dropped
+extern "C" void mga_gwfa_bridge_cells(int32_t out[2]) { out[0] = out[1] = 0; GC_HOST_NOTE(out[0] = gc_host_wf_peak, out[1] = gc_host_wf_pruned;) }
 
 // the assembly alone (mg_gchain_gen, gchain1.c:443-520: records, junctions, bridges, measuring, ordering) from given chain records: CPU parity tests against the reference's function
 extern "C" mg_gchains_t *mga_gchain_gen_host(const gfa_t *g, const gfa_edseq_t *es, int32_t n_u, const uint64_t *u, const mg_lchain_t *lc, const mg128_t *a, int32_t n_a, uint32_t hash,

@@ -277,6 +277,11 @@ int mga_dev_gwfa_wg_jobs(mga_sctx_t *sc, void *jobs, int64_t jobs_cap, int32_t *
 int mga_dev_gwfa_stage(mga_sctx_t *sc, const mga_didx_t *ix, int form, int n_list, const int32_t *d_list, const mga_gwfa_prob_t *d_prob, const char *d_qseq, char *d_arena,
 					   int64_t arena_bytes, int n_groups, int32_t path_cap, int32_t status_ok, int32_t *d_out, int32_t *d_path, unsigned long long *d_counter);
 void mga_dev_gwfa_wg_shape(int *nw, int *cells);
+/* the wide workgroup form (k_gwfa_wgx.hip): the listed problems in list order, a workgroup each; arena blocks of at least 2 MB (their front holds the form's third cell
+ * buffer, the head loop's cells and the step's ranges); d_out / d_path / d_counter as above, a served problem reports MGA_GWFA_WGX */
+int mga_dev_gwfa_wgx_stage(mga_sctx_t *sc, const mga_didx_t *ix, int n_list, const int32_t *d_list, const mga_gwfa_prob_t *d_prob, const char *d_qseq, char *d_arena,
+						   int64_t arena_bytes, int n_groups, int32_t path_cap, int32_t *d_out, int32_t *d_path, unsigned long long *d_counter);
+void mga_dev_gwfa_wgx_shape(int *nw, int *cells_cur, int *cells_wide);
 void mga_gc_wg_count(int64_t served, int64_t back); /* rqphase.c: the counters behind mga_gc_wg_stats */
 /* flat records of one read -> a malloc'ed mg_gchains_t (div and MAPQ computed here, on the host's libm) */
 mg_gchains_t *mga_gchains_from_flat(int32_t n_gc, const void *gc_recs, int32_t n_lc, const mg_llchain_t *lc, int32_t n_a, const mg128_t *a,
@@ -285,6 +290,14 @@ mg_gchains_t *mga_gchains_from_flat(int32_t n_gc, const void *gc_recs, int32_t n
 mg_gchains_t *mga_gchain_host_read(const mg_idx_t *gi, const int32_t *seg_len, const mg_mapopt_t *opt, float pen_gap, int32_t qlen, uint32_t hash,
 								   int32_t n_u, const uint64_t *u, mg128_t *a, int32_t n_a, int32_t n_mini, const int32_t *mini_pos, const char *qseq,
 								   int32_t rep_len, int32_t n_mz, int32_t *n_gwfa, int32_t *n_shortk);
+/* the same in two calls, the contig's bridges between them as problems of mga_gwfa_bridge_batch (-x asm with MGA_ASM_DEV_BRIDGE, batch.c).  u, a, mini_pos and qseq must
+ * live until part 3, which releases the object.  n_jobs: bridges listed, n_q: bases of query they span. */
+typedef struct mga_gcsplit_s mga_gcsplit_t;
+mga_gcsplit_t *mga_gchain_split_p1(const mg_idx_t *gi, const int32_t *seg_len, const mg_mapopt_t *opt, float pen_gap, int32_t qlen, uint32_t hash, int32_t n_u, const uint64_t *u,
+								   mg128_t *a, int32_t n_a, int32_t n_mini, const int32_t *mini_pos, const char *qseq, int32_t *n_jobs, int64_t *n_q);
+void mga_gchain_split_probs(const mga_gcsplit_t *s, mga_gwfa_prob_t *prob, char *qbuf, int64_t q_off);
+mg_gchains_t *mga_gchain_split_p3(mga_gcsplit_t *s, const int32_t *ed, const int32_t *n_path, const int32_t *path, int32_t path_cap, const int32_t *status,
+								  int32_t rep_len, int32_t n_mz);
 
 /* ---- the gap list on the device (k_plan.hip): what align.c:mga_plan_cigar makes on the host, for chains that never left the device ---- */
 typedef struct { /* one graph chain as k_gchain leaves it in the record pool (gc_core.h:gc_rec_t; k_gchain.hip asserts the layouts agree) */

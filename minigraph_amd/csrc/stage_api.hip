@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
+#include <algorithm>
 #include "mga_dev.h"
 #include "dev_common.h"
 
@@ -407,8 +408,15 @@ extern "C" int mga_call_batch(int n_chain, const mga_call_chain_t *chain, int64_
 
 // The bridge between two linear chains as a stage (k_gwfa_wg.hip): n GWFA problems against gi's graph replica.  form MGA_GWFA_FORM_WG: a workgroup per problem; what that form
 // hands back goes through the wave form in a second launch and reports MGA_GWFA_BACK.  form MGA_GWFA_FORM_WAVE: a wavefront per problem, gc_gwfa as k_gchain_p2 runs it.
-// tests/test_gpu_gwfa_wg.py
+// form MGA_GWFA_FORM_WGX: the wide workgroup form (k_gwfa_wgx.hip), one persistent workgroup per compute unit, the problems listed longest query first (the query gap is what
+// is known beforehand of a bridge's cost); its hand-backs take the same second launch.  tests/test_gpu_gwfa_wg.py, tests/test_gpu_gwfa_wgx.py
 extern "C" void mga_gwfa_wg_shape(int *nw, int *cells) { mga_dev_gwfa_wg_shape(nw, cells); }
+extern "C" void mga_gwfa_wgx_shape(int *nw, int *cells_cur, int *cells_wide) { mga_dev_gwfa_wgx_shape(nw, cells_cur, cells_wide); }
+static int64_t g_wgx_stats[2]; // of the wide form's calls since the last reset: the most flagged cells one dedup sorted, the steps replayed with gc_ksort
+extern "C" void mga_gwfa_wgx_stats(int64_t out[2], int reset)
+{
+	for (int i = 0; i < 2; ++i) { out[i] = __atomic_load_n(&g_wgx_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_wgx_stats[i], 0, __ATOMIC_RELAXED); }
+}
 extern "C" int mga_gwfa_bridge_batch(const mg_idx_t *gi, int n, const char *qseq, int64_t n_q, const mga_gwfa_prob_t *prob, int form, int32_t path_cap,
 									  int32_t *ed, int32_t *n_path, int32_t *path, int32_t *status, int32_t *peak)
 {
@@ -416,7 +424,7 @@ extern "C" int mga_gwfa_bridge_batch(const mg_idx_t *gi, int n, const char *qseq
 	mga_sctx_t *SC = mga_sctx_default();
 	if (SC == 0) return -1;
 	if (n <= 0) return 0;
-	if (path_cap < 1 || n_q < 0 || (form != MGA_GWFA_FORM_WAVE && form != MGA_GWFA_FORM_WG)) { mga_set_error("gwfa_bridge_batch: bad arguments"); return -1; }
+	if (path_cap < 1 || n_q < 0 || (form != MGA_GWFA_FORM_WAVE && form != MGA_GWFA_FORM_WG && form != MGA_GWFA_FORM_WGX)) { mga_set_error("gwfa_bridge_batch: bad arguments"); return -1; }
 	const mga_didx_t *ix = &((const mg_idx_bucket_s_view*)gi->B)->dev;
 	const uint32_t n_vtx = gfa_n_vtx(gi->g);
 	for (int i = 0; i < n; ++i) { // the kernels trust the problems: vertices of the graph, offsets inside them, the query inside qseq
@@ -424,19 +432,35 @@ extern "C" int mga_gwfa_bridge_batch(const mg_idx_t *gi, int n, const char *qseq
 		if (p->v0 >= n_vtx || (p->v1 >= n_vtx && p->v1 != (uint32_t)-1) || p->ql < 0 || p->q_off < 0 || p->q_off + p->ql > n_q || p->off0 < 0 || p->off0 >= (int32_t)gi->g->seg[p->v0 >> 1].len ||
 			(p->v1 != (uint32_t)-1 && (p->off1 < 0 || p->off1 >= (int32_t)gi->g->seg[p->v1 >> 1].len))) { mga_set_error("gwfa_bridge_batch: problem %d lies outside the graph or the query", i); return -1; }
 	}
-	const int groups = n < 64 ? n : 64;
+	int groups = n < 64 ? n : 64;
+	if (form == MGA_GWFA_FORM_WGX) { // a workgroup per compute unit
+		int dev = 0, n_cu = 0;
+		MGA_HIP_CHECK(hipGetDevice(&dev));
+		MGA_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+		groups = n < n_cu ? n : n_cu;
+	}
 	const int64_t arena_bytes = 8 << 20; // scratch of a call: the maps and the traceback forest in either form, the wavefronts too in the wave form
 	dptr d_prob, d_q, d_list, d_out, d_path, d_cnt, d_arena;
 	if (!d_prob.alloc((size_t)n * sizeof *prob) || !d_q.alloc((size_t)n_q + 64) || !d_list.alloc((size_t)n * 4) || !d_out.alloc((size_t)n * 16) || !d_path.alloc((size_t)n * path_cap * 4) ||
 		!d_cnt.alloc(64) || !d_arena.alloc((size_t)groups * (size_t)arena_bytes)) return -1;
 	std::vector<int32_t> list((size_t)n), out((size_t)n * 4, 0);
 	for (int i = 0; i < n; ++i) list[(size_t)i] = i;
+	if (form == MGA_GWFA_FORM_WGX) std::stable_sort(list.begin(), list.end(), [prob](int32_t x, int32_t y) { return prob[x].ql > prob[y].ql; });
 	if (mga_h2d(d_prob.p, prob, (size_t)n * sizeof *prob) < 0 || mga_h2d(d_q.p, qseq, (size_t)n_q) < 0 || mga_h2d(d_list.p, list.data(), (size_t)n * 4) < 0 ||
 		mga_h2d(d_out.p, out.data(), (size_t)n * 16) < 0 || mga_dmemset_s(SC, (char*)d_q.p + n_q, 0, 64) < 0 || mga_dmemset_s(SC, d_cnt.p, 0, 64) < 0) return -1;
-	if (mga_dev_gwfa_stage(SC, ix, form, n, d_list.as<int32_t>(), d_prob.as<mga_gwfa_prob_t>(), d_q.as<char>(), d_arena.as<char>(), arena_bytes, groups, path_cap, MGA_GWFA_WAVE,
-						   d_out.as<int32_t>(), d_path.as<int32_t>(), d_cnt.as<unsigned long long>()) < 0) return -1;
+	if (form == MGA_GWFA_FORM_WGX) {
+		if (mga_dev_gwfa_wgx_stage(SC, ix, n, d_list.as<int32_t>(), d_prob.as<mga_gwfa_prob_t>(), d_q.as<char>(), d_arena.as<char>(), arena_bytes, groups, path_cap,
+								   d_out.as<int32_t>(), d_path.as<int32_t>(), d_cnt.as<unsigned long long>()) < 0) return -1;
+	} else if (mga_dev_gwfa_stage(SC, ix, form, n, d_list.as<int32_t>(), d_prob.as<mga_gwfa_prob_t>(), d_q.as<char>(), d_arena.as<char>(), arena_bytes, groups, path_cap, MGA_GWFA_WAVE,
+							  d_out.as<int32_t>(), d_path.as<int32_t>(), d_cnt.as<unsigned long long>()) < 0) return -1;
 	if (mga_ssync(SC) < 0 || mga_d2h(out.data(), d_out.p, (size_t)n * 16) < 0) return -1;
-	if (form == MGA_GWFA_FORM_WG) { // what the workgroup form handed back: once more, a wavefront each
+	if (form == MGA_GWFA_FORM_WGX) {
+		unsigned long long cnt[8];
+		if (mga_d2h(cnt, d_cnt.p, 64) < 0) return -1;
+		if ((int64_t)cnt[1] > __atomic_load_n(&g_wgx_stats[0], __ATOMIC_RELAXED)) __atomic_store_n(&g_wgx_stats[0], (int64_t)cnt[1], __ATOMIC_RELAXED);
+		__atomic_fetch_add(&g_wgx_stats[1], (int64_t)cnt[2], __ATOMIC_RELAXED);
+	}
+	if (form != MGA_GWFA_FORM_WAVE) { // what a workgroup form handed back: once more, a wavefront each
 		int n_back = 0;
 		for (int i = 0; i < n; ++i) if (out[(size_t)i * 4 + 2] == MGA_GWFA_BACK) list[(size_t)n_back++] = i;
 		if (n_back > 0) {
