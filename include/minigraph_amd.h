@@ -473,6 +473,20 @@ int mga_lchain_batch(int n, const mg128_t *a, const int64_t *a_off, const mga_lc
 int mga_sort128x_batch(int n, mg128_t *a, const int64_t *a_off);
 /* the dv:f: field of a GAF line as the device prints it (k_gaf.hip; format.c:200-203: "%.4f", "0" for zero): out = n x 8 bytes, NUL-padded (tests) */
 int mga_gaf_div_batch(int n, const float *div, char *out);
+/* Whole GAF lines (mg_write_gaf, format.c:121-250) as the device writes them, as a stage: n_lines line records (mga_gaf_line_t, mga_dev.h) over n_chain chains (mga_txt_chain_t:
+ * vert_beg / vert_cnt are read) with their walks in vert[n_vert] and their text results (mga_txt_res_t: cg:Z at pool + txt_off, ds:Z behind it, mlen, blen), the reads' names
+ * back to back (read r = qnames[qname_off[r] .. qname_off[r + 1])), against gi's name tables.  form MGA_GAF_FORM_WAVE: a wavefront per line (k_gaf.hip); MGA_GAF_FORM_WIDE: a
+ * workgroup per line, the path column built by scans over tiles of mga_gaf_wide_tile() vertices (k_gaf_wide.hip).  *out (mga_free) = the lines back to back,
+ * out_off[n_lines + 1] their offsets.  Returns 1 (no text) if the wide form met a line of 2^31 bytes or more.
+ * Environment of the mapping path: MGA_DEV_GAF_WIDE=1 writes the lines of a chunk of chromosome-scale chains (-x asm: MGA_GAF_WIDE_MIN = 32768 or more plan items + CIGAR
+ * operators per chain) with the wide form instead of the host writer; unset or 0: as before.  mga_gaf_wide_stats: out[0] lines the wide form wrote, out[1] chunks it handed
+ * to the host writer because a line's length does not fit 32 bits, since the last reset. */
+#define MGA_GAF_FORM_WAVE 0
+#define MGA_GAF_FORM_WIDE 1
+int mga_gaf_lines_batch(const mg_idx_t *gi, int n_lines, const void *lines, int n_reads, const char *qnames, const int64_t *qname_off, uint64_t flag, int n_chain, const void *chains,
+						int64_t n_vert, const uint32_t *vert, const void *tres, const char *pool, int64_t pool_len, int form, char **out, int64_t *out_off);
+int mga_gaf_wide_tile(void);
+void mga_gaf_wide_stats(int64_t out[2], int reset);
 
 /* mwf_wfa_auto's exact mode (miniwfa.c:380-435,603-615,824-828) for n independent problems:
  * target i = tseq[t_off[i]..t_off[i+1]), query i = qseq[q_off[i]..q_off[i+1]) (raw ASCII compare).

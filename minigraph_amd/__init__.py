@@ -62,7 +62,7 @@ MG_M_CIGAR = 0x4000000
 
 KERNELS = ["k_sketch", "k_seed_count", "k_seed_fill", "k_lchain", "k_wfa_r[64]", "k_wfa_r[128]", "k_wfa_r[192]", "k_wfa_r[256]", "k_wfa_r[512]",
            "k_wfa_r[1024]", "k_wfa_r[2048]", "k_wfa[hbm4096]", "k_wfa[hbm32768]", "k_scan", "k_text", "k_gchain", "k_plan",
-           "k_wfa_w[16x4]", "k_wfa_w[32x2]", "k_wfa_w[64]", "k_wfa_w[128]", "k_wfa_w[192]", "k_wfa_w[256]", "k_wfa_tb", "k_gchain_p2", "k_gchain_p3", "k_gaf", "k_cov"]
+           "k_wfa_w[16x4]", "k_wfa_w[32x2]", "k_wfa_w[64]", "k_wfa_w[128]", "k_wfa_w[192]", "k_wfa_w[256]", "k_wfa_tb", "k_gchain_p2", "k_gchain_p3", "k_gaf", "k_cov", "k_gaf_wide"]
 
 
 class stats_t(C.Structure):  # mga_stats_t
@@ -428,6 +428,65 @@ def gaf_div_batch(div):
     L.mga_gaf_div_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     _check(L.mga_gaf_div_batch(len(div), div.ctypes.data, out.ctypes.data), "mga_gaf_div_batch")
     return [bytes(out[8 * i:8 * i + 8]).rstrip(b"\0") for i in range(len(div))]
+
+
+gaf_line_dtype = np.dtype([(n, "<i4") for n in ("read", "chain", "qlen", "qs", "qe", "plen", "ps", "pe", "mapq", "n_anchor", "score", "subsc", "primary")] + [("div", "<f4")])   # mga_gaf_line_t
+txt_chain_dtype = np.dtype([(n, "<i8") for n in ("item_beg", "item_end", "prob_base", "q_base", "vert_beg")] +
+                           [(n, "<i4") for n in ("vert_cnt", "qs", "qe", "ss", "ee", "ps", "pe", "rev_sign")])   # mga_txt_chain_t
+txt_res_dtype = np.dtype([("txt_off", "<i8")] + [(n, "<i4") for n in ("cg_len", "ds_len", "n_cigar", "mlen", "blen", "aplen", "status", "pad")])   # mga_txt_res_t
+MG_M_VERTEX_COOR, MG_M_NO_COMP_PATH = 0x800, 0x200000
+
+
+def gaf_wide_tile():
+    """vertices of a tile (= threads of a workgroup) of the wide form of the GAF line kernel (k_gaf_wide.hip)"""
+    return int(load().mga_gaf_wide_tile())
+
+
+def gaf_wide_stats(reset=False):
+    """of the mapping path under MGA_DEV_GAF_WIDE=1 since the last reset: lines the wide form wrote / chunks it handed to the host writer for a line's length"""
+    st = (C.c_int64 * 2)()
+    load().mga_gaf_wide_stats(st, 1 if reset else 0)
+    return {"lines": st[0], "too_long": st[1]}
+
+
+def gaf_wide_route(status):
+    """what a chunk does with the wide launcher's answer: 0 the device's lines stand, 1 the chunk goes to the host writer, -1 an error (no GPU needed)"""
+    return int(load().mga_gaf_wide_route(int(status)))
+
+
+def gaf_len32(total):
+    """a line's 64-bit byte count as the wide kernel stores it in its int32 length: the count, or -1 (no GPU needed)"""
+    L = load()
+    L.mga_gaf_len32_host.argtypes, L.mga_gaf_len32_host.restype = [C.c_int64], C.c_int32
+    return int(L.mga_gaf_len32_host(total))
+
+
+def gaf_lines_batch(graph, qnames, lines, walks, mlen_blen, strings, pool, flag=0, form="wide"):
+    """whole GAF lines on the device against the graph's name tables.  qnames: the reads' names (bytes); lines: mga_gaf_line_t fields as dicts (read, chain = index into
+    walks or -1 for an unmapped read's line, qlen, qs, ...); walks: one array of oriented vertices per chain; mlen_blen: (mlen, blen) per chain; strings: (offset of cg:Z in
+    pool, cg length, ds length) per chain, ds:Z behind cg:Z; form "wave": a wavefront per line, "wide": a workgroup per line -> (the lines as bytes, their offsets)"""
+    L = load()
+    n, nc = len(lines), len(walks)
+    ln = np.zeros(n, dtype=gaf_line_dtype)
+    for i, d in enumerate(lines):
+        for k, v in d.items():
+            ln[i][k] = v
+    ch, tr = np.zeros(nc + 1, dtype=txt_chain_dtype), np.zeros(nc + 1, dtype=txt_res_dtype)
+    vert = np.ascontiguousarray(np.concatenate([np.asarray(w, dtype=np.uint32) for w in walks]) if nc else np.zeros(0, dtype=np.uint32))
+    for i, w in enumerate(walks):
+        ch[i]["vert_beg"], ch[i]["vert_cnt"] = sum(len(x) for x in walks[:i]), len(w)
+        tr[i]["txt_off"], tr[i]["cg_len"], tr[i]["ds_len"] = strings[i]
+        tr[i]["mlen"], tr[i]["blen"] = mlen_blen[i]
+    names, q_off = concat(qnames)
+    off, out = np.zeros(n + 1, dtype=np.int64), C.c_void_p()
+    L.mga_gaf_lines_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p,
+                                      C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    rc = L.mga_gaf_lines_batch(graph.gi, n, ln.ctypes.data, len(qnames), names, q_off.ctypes.data, flag, nc, ch.ctypes.data, len(vert), vert.ctypes.data, tr.ctypes.data, pool, len(pool),
+                               {"wave": 0, "wide": 1}[form], C.byref(out), off.ctypes.data)
+    if rc == 1:
+        raise OverflowError("a GAF line of 2^31 bytes or more")
+    _check(rc, "mga_gaf_lines_batch")
+    return bytes(_take(out, int(off[-1]), np.uint8)), off
 
 
 def sort128x_batch(arrays):

@@ -131,6 +131,17 @@ static int64_t gaf_lines_build(const mga_batch_t *b, int n, mga_gaf_line_t *line
 	return nl;
 }
 
+/* the wide launcher's answer, as chunk_gaf_dev() takes it: 0 the device's lines stand; 1 a line's bytes do not fit line_len's int32: the chunk goes to the host writer
+ * as it did before there was a wide form; -1 an error */
+int mga_gaf_wide_route(int rc) { return rc == 0 ? 0 : rc == MGA_GAF_WIDE_TOO_LONG ? 1 : -1; }
+
+static int64_t g_gaf_wide_stats[2]; /* since the last reset: lines the wide form wrote, chunks it handed to the host writer for a line's length */
+void mga_gaf_wide_stats(int64_t out[2], int reset)
+{
+	int i;
+	for (i = 0; i < 2; ++i) { out[i] = __atomic_load_n(&g_gaf_wide_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_gaf_wide_stats[i], 0, __ATOMIC_RELAXED); }
+}
+
 typedef struct { char *dst; const char *src; int64_t bytes; int T; } pcopy_t;
 static void pcopy_worker(void *data, int64_t t, int tid) { pcopy_t *c = (pcopy_t*)data; const int64_t b = c->bytes * t / c->T, e = c->bytes * (t + 1) / c->T; (void)tid; if (e > b) memcpy(c->dst + b, c->src + b, (size_t)(e - b)); }
 
@@ -156,6 +167,8 @@ typedef struct {
 	int txt_tight;      /* MGA_TXT_TIGHT=1: a deliberately small text pool, so that a test sees the second launch */
 	int dev_gaf;        /* MGA_DEV_GAF=0: the host formats the GAF lines as in rounds 1-5 (A/B, tests) */
 	int gaf_direct;     /* MGA_GAF_DIRECT=0: a chunk's lines always go through its pieces, never straight to their place in the job's output */
+	int dev_gaf_wide;   /* MGA_DEV_GAF_WIDE=1: the lines of chromosome-scale chains (-x asm) are written on the device as well, a workgroup per line (k_gaf_wide.hip); otherwise by the host writer */
+	int gaf_wide_min;   /* MGA_GAF_WIDE_MIN: plan items + CIGAR operators per chain from which a chunk's chains count as chromosome-scale (default 32768; the tests lower it) */
 } chunk_knobs_t;
 
 static void chunk_knobs_read(chunk_knobs_t *k)
@@ -167,6 +180,7 @@ static void chunk_knobs_read(chunk_knobs_t *k)
 	k->check = env_int("MGA_CHECK", 0), k->dev_splice = env_int("MGA_DEV_SPLICE", 1), k->dev_rmq = env_int("MGA_DEV_RMQ", 1);
 	k->dev_lcdp = env_int("MGA_DEV_LCDP", 0);
 	k->txt_tight = env_int("MGA_TXT_TIGHT", 0), k->dev_gaf = env_int("MGA_DEV_GAF", 1), k->gaf_direct = env_int("MGA_GAF_DIRECT", 1);
+	k->dev_gaf_wide = env_int("MGA_DEV_GAF_WIDE", 0), k->gaf_wide_min = env_int("MGA_GAF_WIDE_MIN", 32768);
 }
 
 typedef struct { /* one run of the stage sequence: a stack object of map_chunk() */
@@ -717,21 +731,22 @@ static int chunk_text(chunk_t *c)
 }
 
 /* Round 6: the whole LINES are written on the device (k_gaf.hip) -- name, coordinates, path column, tags in front of the two strings, every line at its place in
- * the chunk's text -- unless the job asks for what only the host's writer prints (per-vertex lines of -S / --write-mz) or the chains are chromosome-scale
- * (their walks have 10^5 vertices: one wavefront per line would fold them alone); then the strings come down for the host's writer.  Either way the text results land here. */
+ * the chunk's text -- unless the job asks for what only the host's writer prints (per-vertex lines of -S / --write-mz).  Chromosome-scale chains (their walks have 10^5
+ * vertices: one wavefront per line would fold them alone) take the workgroup form (k_gaf_wide.hip) under MGA_DEV_GAF_WIDE=1; without it, or when a line's bytes do not fit
+ * an int32, the strings come down for the host's writer.  Either way the text results land here. */
 static int chunk_gaf_dev(chunk_t *c)
 {
 	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc; struct mg_idx_bucket_s *B = c->in.gi->B; const mg_mapopt_t *opt = c->in.opt; mga_batch_t *b = c->b; const int n = c->in.n; const char **qnames = c->in.qnames;
 	const int64_t n_chain = c->n_chain;
 	int64_t n_lines = -1, k;
-	int i;
+	int i, wide = 0;
 	if (c->in.gaf_part && B->dev.d_gaf_seg != 0 && !(opt->flag & (MG_M_WRITE_LCHAIN | MG_M_WRITE_MZ | MG_M_FRAG_MERGE)) && !(mg_dbg_flag & 0x8) && n_chain > 0 &&
-		(c->n_item + c->n_ops) / n_chain < 32768 && n_chain < 0x7fffffffLL && c->k.dev_gaf) {
+		((wide = (c->n_item + c->n_ops) / n_chain >= c->k.gaf_wide_min) == 0 || c->k.dev_gaf_wide) && n_chain < 0x7fffffffLL && c->k.dev_gaf) {
 		CK(mga_hbuf_reserve(&P->h_gline, (size_t)(n_chain + n) * sizeof(mga_gaf_line_t) + 64));
 		n_lines = gaf_lines_build(b, n, (mga_gaf_line_t*)P->h_gline.p);
 	}
 	if (n_lines > 0) { /* line records and names up, then count -> scan -> write */
-		int64_t qn_bytes = 0, tot_b = 0, *qo;
+		int64_t qn_bytes = 0, *qo;
 		char *qn;
 		for (i = 0; i < n; ++i) qn_bytes += qnames ? (int64_t)strlen(qnames[i]) : 1;
 		CK(mga_hbuf_reserve(&P->h_gqn, (size_t)(n + 1) * 8 + (size_t)qn_bytes + 64));
@@ -741,13 +756,23 @@ static int chunk_gaf_dev(chunk_t *c)
 		CK(mga_dbuf_reserve(&P->g_line, (size_t)n_lines * sizeof(mga_gaf_line_t) + 64)); CK(mga_dbuf_reserve(&P->g_qoff, (size_t)(n + 1) * 8)); CK(mga_dbuf_reserve(&P->g_qn, (size_t)qn_bytes + 64));
 		CK(mga_dbuf_reserve(&P->g_len, (size_t)(n_lines + 1) * 4)); CK(mga_dbuf_reserve(&P->g_off, (size_t)(n_lines + 2) * 8));
 		CK(mga_h2d_s(sc, P->g_line.p, P->h_gline.p, (size_t)n_lines * sizeof(mga_gaf_line_t))); CK(mga_h2d_s(sc, P->g_qoff.p, qo, (size_t)(n + 1) * 8)); CK(mga_h2d_s(sc, P->g_qn.p, qn, (size_t)qn_bytes + 1));
-		CK(mga_dev_gaf(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
-					   (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, 0, 0));
+		if (wide) { /* a workgroup per line; a line past 2^31 bytes sends the chunk to the host writer */
+			const int route = mga_gaf_wide_route(mga_dev_gaf_wide(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag,
+									(const mga_txt_chain_t*)P->chain.p, (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, 0, 0));
+			if (route < 0) return -1;
+			if (route > 0) { __atomic_fetch_add(&g_gaf_wide_stats[1], 1, __ATOMIC_RELAXED); n_lines = -1; }
+		} else
+			CK(mga_dev_gaf(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
+						   (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, 0, 0));
+	}
+	if (n_lines > 0) {
+		int64_t tot_b = 0;
 		CK(mga_dev_scan_i32_to_i64(sc, (const int32_t*)P->g_len.p, n_lines, (int64_t*)P->g_off.p));
 		CK(mga_d2h_s(sc, &tot_b, (int64_t*)P->g_off.p + n_lines, 8)); CK(mga_ssync(sc));
 		CK(mga_dbuf_reserve(&P->g_out, (size_t)tot_b + 64)); CK(mga_hbuf_reserve(&P->h_gout, (size_t)tot_b + 64));
-		CK(mga_dev_gaf(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
+		CK((wide ? mga_dev_gaf_wide : mga_dev_gaf)(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
 					   (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, (const int64_t*)P->g_off.p, (char*)P->g_out.p));
+		if (wide) __atomic_fetch_add(&g_gaf_wide_stats[0], n_lines, __ATOMIC_RELAXED);
 		if (tot_b > 0) CK(mga_d2h_s(sc, P->h_gout.p, P->g_out.p, (size_t)tot_b));
 		b->gaf_dev = (const char*)P->h_gout.p, b->gaf_dev_len = tot_b;
 	} else if (n_lines == 0) b->gaf_dev = "", b->gaf_dev_len = 0; /* (nothing of this chunk is printed) */

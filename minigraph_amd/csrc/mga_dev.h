@@ -78,7 +78,7 @@ void mga_hbuf_free(mga_hbuf_t *b);
 
 /* per-kernel HIP-event timing on the launch stream (bench.py reads it through mga_prof_get) */
 enum { MGA_K_SKETCH = 0, MGA_K_SEED_COUNT, MGA_K_SEED_FILL, MGA_K_LCHAIN, MGA_K_WFA0 /* +tier: 0-2 single-wave register tiers (band 64,128,192), 3-6 multi-wave register tiers (256..2048), 7-8 HBM tiers */, MGA_K_SCAN = MGA_K_WFA0 + 9, MGA_K_TEXT, MGA_K_GCHAIN, MGA_K_PLAN,
-	   MGA_K_WFAW0 /* +0..5: windowed tiers of 16 (4 problems per wave), 32 (2), 64, 128, 192, 256 diagonals (k_wfa_w.hip) */, MGA_K_WFATB = MGA_K_WFAW0 + 6 /* their traceback */, MGA_K_GCHAIN2 /* graph chaining, three-kernel form: part 2 (a wavefront per bridge) */, MGA_K_GCHAIN3 /* part 3; part 1 counts as MGA_K_GCHAIN */, MGA_K_GAF /* whole GAF lines (k_gaf.hip) */, MGA_K_COV /* read coverage (k_cov.hip) */, MGA_K_N };
+	   MGA_K_WFAW0 /* +0..5: windowed tiers of 16 (4 problems per wave), 32 (2), 64, 128, 192, 256 diagonals (k_wfa_w.hip) */, MGA_K_WFATB = MGA_K_WFAW0 + 6 /* their traceback */, MGA_K_GCHAIN2 /* graph chaining, three-kernel form: part 2 (a wavefront per bridge) */, MGA_K_GCHAIN3 /* part 3; part 1 counts as MGA_K_GCHAIN */, MGA_K_GAF /* whole GAF lines (k_gaf.hip) */, MGA_K_COV /* read coverage (k_cov.hip) */, MGA_K_GAFW /* whole GAF lines, a workgroup per line (k_gaf_wide.hip) */, MGA_K_N };
 #define MGA_WFW_N 6         /* windowed tiers */
 #define MGA_WFA_N_TIER 9    /* register + HBM tiers (k_wfa_r.hip 0-6, k_wfa.hip 7-8) */
 #define MGA_WFA_N_SLOT 11   /* rungs of the ladder: W0-W5, R4-R6, H0-H1 (MGA_WFA_LADDER=old: R0-R6, H0-H1) */
@@ -236,6 +236,16 @@ int mga_dev_gaf_div(mga_sctx_t *sc, int n, const float *d_div, char *d_out); /* 
 /* d_out == NULL: d_len[i] = bytes of line i; else: line i at d_out + d_off[i].  Lines are the caller's: printed chains of the chunk in read order */
 int mga_dev_gaf(mga_sctx_t *sc, const mga_didx_t *ix, int n_lines, const mga_gaf_line_t *d_line, const char *d_qnames, const int64_t *d_qname_off, uint64_t flag,
 				const mga_txt_chain_t *d_chain, const uint32_t *d_vert, const mga_txt_res_t *d_tres, const char *d_tpool, int32_t *d_len, const int64_t *d_off, char *d_out);
+/* the same two passes with a workgroup per line and the path column built by scans (k_gaf_wide.hip): for chromosome-scale walks.  d_len has n_lines + 1 entries: pass 1 stores
+ * -1 for a line whose bytes do not fit an int32 and counts those lines in d_len[n_lines]; it waits for the kernel and returns MGA_GAF_WIDE_TOO_LONG if there is one (nothing is
+ * clamped: the caller's lines then go to the host writer) */
+#define MGA_GAF_WIDE_TOO_LONG 1
+int mga_dev_gaf_wide(mga_sctx_t *sc, const mga_didx_t *ix, int n_lines, const mga_gaf_line_t *d_line, const char *d_qnames, const int64_t *d_qname_off, uint64_t flag,
+					 const mga_txt_chain_t *d_chain, const uint32_t *d_vert, const mga_txt_res_t *d_tres, const char *d_tpool, int32_t *d_len, const int64_t *d_off, char *d_out);
+int mga_dev_gaf_wide_tile(void);              /* vertices of a tile = threads of a workgroup */
+int32_t mga_gaf_len32_host(int64_t total);    /* a line's 64-bit byte count as the kernel stores it in d_len: the count, or -1 */
+/* chunk.c: what a chunk does with the wide launcher's answer: 0 the device's lines stand, 1 the chunk goes to the host writer, -1 an error */
+int mga_gaf_wide_route(int rc);
 
 /* ---- read coverage on the device (k_cov.hip, cov_core.h): mg_cov_map, cal_cov.c:8-53, as integer sums ----
  * chain records + walk vertices of a chunk are ADDED into d_seg_bases[n_seg] / d_link_cnt[n_arc] / d_cnt[MGA_COV_N_CNT] (the job's accumulators: zeroed by the caller, once) */

@@ -202,6 +202,59 @@ extern "C" int mga_gaf_div_batch(int n, const float *div, char *out)
 	return 0;
 }
 
+// Whole GAF lines as a stage: the records a chunk would hand to mga_dev_gaf / mga_dev_gaf_wide, from host arrays; count -> scan -> write as chunk_gaf_dev() runs them.
+// tests/test_gpu_gaf_wide.py
+extern "C" int mga_gaf_wide_tile(void) { return mga_dev_gaf_wide_tile(); }
+extern "C" int mga_gaf_lines_batch(const mg_idx_t *gi, int n_lines, const void *lines, int n_reads, const char *qnames, const int64_t *qname_off, uint64_t flag, int n_chain, const void *chains,
+								   int64_t n_vert, const uint32_t *vert, const void *tres, const char *pool, int64_t pool_len, int form, char **out, int64_t *out_off)
+{
+	*out = 0;
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	const mga_didx_t *ix = &((const mg_idx_bucket_s_view*)gi->B)->dev;
+	const mga_gaf_line_t *ln = (const mga_gaf_line_t*)lines;
+	const mga_txt_chain_t *ch = (const mga_txt_chain_t*)chains;
+	const mga_txt_res_t *tr = (const mga_txt_res_t*)tres;
+	if (n_lines < 0 || n_reads < 0 || n_chain < 0 || n_vert < 0 || pool_len < 0 || (form != MGA_GAF_FORM_WAVE && form != MGA_GAF_FORM_WIDE)) { mga_set_error("gaf_lines_batch: bad arguments"); return -1; }
+	out_off[0] = 0;
+	if (n_lines == 0) return 0;
+	const uint32_t n_vtx = gfa_n_vtx(gi->g);
+	for (int i = 0; i < n_chain; ++i) { // the kernels trust the records: walks inside vert[], vertices of the graph, strings inside the pool
+		if (ch[i].vert_cnt < 1 || ch[i].vert_beg < 0 || ch[i].vert_beg + ch[i].vert_cnt > n_vert || tr[i].cg_len < 0 || tr[i].ds_len < 0 || tr[i].txt_off < 0 ||
+			tr[i].txt_off + tr[i].cg_len + tr[i].ds_len > pool_len) { mga_set_error("gaf_lines_batch: chain %d points outside the walk vertices or the text pool", i); return -1; }
+		for (int32_t j = 0; j < ch[i].vert_cnt; ++j)
+			if (vert[ch[i].vert_beg + j] >= n_vtx) { mga_set_error("gaf_lines_batch: chain %d walks over a vertex the graph does not have", i); return -1; }
+	}
+	for (int i = 0; i < n_lines; ++i)
+		if (ln[i].read < 0 || ln[i].read >= n_reads || ln[i].chain >= n_chain) { mga_set_error("gaf_lines_batch: line %d names a read or a chain that is not there", i); return -1; }
+	for (int i = 0; i < n_reads; ++i)
+		if (qname_off[i] < 0 || qname_off[i + 1] < qname_off[i]) { mga_set_error("gaf_lines_batch: the name offsets do not ascend"); return -1; }
+	const int64_t qn_bytes = n_reads > 0 ? qname_off[n_reads] : 0;
+	dptr d_line, d_qn, d_qoff, d_chain, d_vert, d_tres, d_pool, d_len, d_off, d_out;
+	if (!d_line.alloc((size_t)n_lines * sizeof *ln) || !d_qn.alloc((size_t)qn_bytes + 64) || !d_qoff.alloc((size_t)(n_reads + 1) * 8) || !d_chain.alloc((size_t)(n_chain + 1) * sizeof *ch) ||
+		!d_vert.alloc((size_t)n_vert * 4 + 16) || !d_tres.alloc((size_t)(n_chain + 1) * sizeof *tr) || !d_pool.alloc((size_t)pool_len + 64) || !d_len.alloc((size_t)(n_lines + 1) * 4) ||
+		!d_off.alloc((size_t)(n_lines + 2) * 8)) return -1;
+	if (mga_h2d(d_line.p, ln, (size_t)n_lines * sizeof *ln) < 0 || (qn_bytes > 0 && mga_h2d(d_qn.p, qnames, (size_t)qn_bytes) < 0) || mga_h2d(d_qoff.p, qname_off, (size_t)(n_reads + 1) * 8) < 0 ||
+		(n_chain > 0 && (mga_h2d(d_chain.p, ch, (size_t)n_chain * sizeof *ch) < 0 || mga_h2d(d_tres.p, tr, (size_t)n_chain * sizeof *tr) < 0)) ||
+		(n_vert > 0 && mga_h2d(d_vert.p, vert, (size_t)n_vert * 4) < 0) || (pool_len > 0 && mga_h2d(d_pool.p, pool, (size_t)pool_len) < 0)) return -1;
+	auto pass = form == MGA_GAF_FORM_WIDE ? mga_dev_gaf_wide : mga_dev_gaf;
+	const int rc = pass(SC, ix, n_lines, d_line.as<mga_gaf_line_t>(), d_qn.as<char>(), d_qoff.as<int64_t>(), flag, d_chain.as<mga_txt_chain_t>(), d_vert.as<uint32_t>(),
+						d_tres.as<mga_txt_res_t>(), d_pool.as<char>(), d_len.as<int32_t>(), 0, 0);
+	if (rc != 0) return rc;
+	if (mga_dev_scan_i32_to_i64(SC, d_len.as<int32_t>(), n_lines, d_off.as<int64_t>()) < 0) return -1;
+	if (mga_ssync(SC) < 0 || mga_d2h(out_off, d_off.p, (size_t)(n_lines + 1) * 8) < 0) return -1;
+	const int64_t tot = out_off[n_lines];
+	char *h = (char*)malloc((size_t)tot + 1);
+	if (h == 0 || !d_out.alloc((size_t)tot + 64)) { free(h); mga_set_error("gaf_lines_batch: out of memory"); return -1; }
+	if (mga_dmemset_s(SC, d_out.p, 0, (size_t)tot + 64) < 0) { free(h); return -1; } // (a byte no thread wrote reads as NUL)
+	if (pass(SC, ix, n_lines, d_line.as<mga_gaf_line_t>(), d_qn.as<char>(), d_qoff.as<int64_t>(), flag, d_chain.as<mga_txt_chain_t>(), d_vert.as<uint32_t>(), d_tres.as<mga_txt_res_t>(),
+			 d_pool.as<char>(), d_len.as<int32_t>(), d_off.as<int64_t>(), d_out.as<char>()) < 0 || mga_ssync(SC) < 0 || (tot > 0 && mga_d2h(h, d_out.p, (size_t)tot) < 0)) { free(h); return -1; }
+	h[tot] = 0;
+	*out = h;
+	return 0;
+}
+
 extern "C" int mga_sort128x_batch(int n, mg128_t *a, const int64_t *a_off)
 {
 	if (mga_dev_init() < 0) return -1;
