@@ -487,6 +487,19 @@ int mga_gaf_lines_batch(const mg_idx_t *gi, int n_lines, const void *lines, int 
 						int64_t n_vert, const uint32_t *vert, const void *tres, const char *pool, int64_t pool_len, int form, char **out, int64_t *out_off);
 int mga_gaf_wide_tile(void);
 void mga_gaf_wide_stats(int64_t out[2], int reset);
+/* The per-vertex lines of -S / --write-mz (MG_M_WRITE_LCHAIN, MG_M_WRITE_MZ; format.c:252-289) are written on the device as well (k_gaf_vert.hip), behind each chain's line, for
+ * every chunk whose lines the wavefront form of the line kernel writes, and in jobs without -c, where the host writer formats each chain's line and copies the device's vertex
+ * lines behind it; MGA_DEV_GAF_VERT=0 keeps the host writer for such jobs.  A chunk goes back to the host writer when a
+ * vertex's div = log(n_mz / cnt) / span lies within 1e-9 (in units of the fourth decimal) of a rounding boundary of "%.4f" -- the device's log is not glibc's bit for bit --,
+ * when a line passes 2^31 bytes, and when its chains are chromosome-scale (the wide form).  mga_gaf_vert_stats: out[0] vertex lines the device wrote, out[1] chunks handed back
+ * for a div, out[2] chunks handed back for size or wide routing, since the last reset.
+ * mga_gaf_vert_batch is that path as a stage, on hand-made chains: read r has the chains chains[gc_off[r] .. gc_off[r + 1]) (none: the line of an unmapped read under
+ * MG_M_SHOW_UNMAP); a chain's walk is lc[lc_off .. lc_off + cnt), a record's anchors a[off .. off + cnt), its cg:Z / ds:Z text lies at pool + txt_off.  route 0: the device
+ * (k_gaf + k_gaf_vert; a hand-back ends in the host writer and is counted like a chunk's), route 1: the host writer (gaf.c).  *out (mga_free) = the lines, *out_len their bytes. */
+typedef struct { int32_t id, parent, lc_off, cnt, n_anchor, score, subsc, qs, qe, plen, ps, pe, mapq, mlen, blen; float div; int64_t txt_off; int32_t cg_len, ds_len; } mga_gaf_vchain_t;
+int mga_gaf_vert_batch(const mg_idx_t *gi, int n_reads, const char *qnames, const int64_t *qname_off, const int32_t *qlens, const int64_t *gc_off, const mga_gaf_vchain_t *chains,
+					   int64_t n_lc, const mg_llchain_t *lc, int64_t n_a, const mg128_t *a, const char *pool, int64_t pool_len, uint64_t flag, int route, char **out, int64_t *out_len);
+void mga_gaf_vert_stats(int64_t out[3], int reset);
 
 /* mwf_wfa_auto's exact mode (miniwfa.c:380-435,603-615,824-828) for n independent problems:
  * target i = tseq[t_off[i]..t_off[i+1]), query i = qseq[q_off[i]..q_off[i+1]) (raw ASCII compare).

@@ -449,6 +449,45 @@ def gaf_wide_stats(reset=False):
     return {"lines": st[0], "too_long": st[1]}
 
 
+def gaf_vert_stats(reset=False):
+    """of the per-vertex lines of -S / --write-mz (k_gaf_vert.hip) since the last reset: lines the device wrote / chunks handed to the host writer for a div on a rounding
+    boundary / chunks handed back for a line's size or wide routing"""
+    st = (C.c_int64 * 3)()
+    load().mga_gaf_vert_stats(st, 1 if reset else 0)
+    return st[0], st[1], st[2]
+
+
+gaf_vchain_dtype = np.dtype([(n, "<i4") for n in ("id", "parent", "lc_off", "cnt", "n_anchor", "score", "subsc", "qs", "qe", "plen", "ps", "pe", "mapq", "mlen", "blen")] +
+                            [("div", "<f4"), ("txt_off", "<i8"), ("cg_len", "<i4"), ("ds_len", "<i4")])   # mga_gaf_vchain_t
+llchain_dtype = np.dtype([("off", "<i4"), ("cnt", "<i4"), ("v", "<u4"), ("score", "<i4"), ("ed", "<i4")])   # mg_llchain_t
+
+
+def gaf_vert_batch(graph, qnames, qlens, chains, lc, a, pool, flag, route="device"):
+    """the GAF lines of hand-made chains with their per-vertex lines (-S / --write-mz).  chains: per read a list of mga_gaf_vchain_t fields as dicts (lc_off / cnt: the
+    chain's walk in lc); lc: mg_llchain_t records (off, cnt, v[, score, ed]), off / cnt into a; a: anchors (x, y); route "device": k_gaf + k_gaf_vert, "host": gaf.c -> bytes"""
+    L = load()
+    ch = np.zeros(sum(len(c) for c in chains) + 1, dtype=gaf_vchain_dtype)
+    gc_off = np.zeros(len(chains) + 1, dtype=np.int64)
+    for r, cs in enumerate(chains):
+        gc_off[r + 1] = gc_off[r] + len(cs)
+        for i, d in enumerate(cs):
+            for k, v in d.items():
+                ch[gc_off[r] + i][k] = v
+    lcs = np.zeros(len(lc) + 1, dtype=llchain_dtype)
+    for i, t in enumerate(lc):
+        lcs[i]["off"], lcs[i]["cnt"], lcs[i]["v"] = t[:3]
+    an = np.zeros(len(a) + 1, dtype=m128)
+    an[:len(a)] = a
+    names, q_off = concat(qnames)
+    ql = np.ascontiguousarray(qlens, dtype=np.int32)
+    out, n = C.c_void_p(), C.c_int64()
+    L.mga_gaf_vert_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_int64,
+                                     C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    _check(L.mga_gaf_vert_batch(graph.gi, len(chains), names, q_off.ctypes.data, ql.ctypes.data, gc_off.ctypes.data, ch.ctypes.data, len(lc), lcs.ctypes.data, len(a), an.ctypes.data,
+                                pool, len(pool), flag, {"device": 0, "host": 1}[route], C.byref(out), C.byref(n)), "mga_gaf_vert_batch")
+    return bytes(_take(out, n.value, np.uint8))
+
+
 def gaf_wide_route(status):
     """what a chunk does with the wide launcher's answer: 0 the device's lines stand, 1 the chunk goes to the host writer, -1 an error (no GPU needed)"""
     return int(load().mga_gaf_wide_route(int(status)))

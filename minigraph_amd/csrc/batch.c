@@ -487,7 +487,7 @@ void gaf_worker(void *data, int64_t t, int tid)
 		if (bt->txt_res && gcs && pl->chain_id) {
 			if (gcs->n_gc > m_txt) { m_txt = gcs->n_gc + 8; txt = MGA_REALLOC(mga_chain_text_t, txt, m_txt); }
 			for (k = 0; k < gcs->n_gc; ++k) {
-				txt[k].cg = txt[k].ds = 0;
+				txt[k].cg = txt[k].ds = txt[k].vt = 0;
 				if (pl->chain_id[k] >= 0) {
 					const mga_txt_res_t *r = &bt->txt_res[pl->tid < 0 ? pl->chain_id[k] : bt->dp_n_chain + bt->tp_chain_base[pl->tid] + pl->chain_id[k]]; /* device-planned chains first, then the pools' */
 					txt[k].cg = bt->txt_pool + r->txt_off, txt[k].ds = txt[k].cg + r->cg_len;
@@ -497,6 +497,15 @@ void gaf_worker(void *data, int64_t t, int tid)
 						txt[k].cg_len = txt[k].ds_len = 0;
 					}
 				}
+			}
+			tx = txt;
+		} else if (bt->vert_dev && gcs && gcs->n_gc > 0) { /* no -c: the lines are formatted here, the per-vertex lines behind each of them come from the device (mode 0 only: no txt_res) */
+			int64_t l = bt->vert_line0[i];
+			if (gcs->n_gc > m_txt) { m_txt = gcs->n_gc + 8; txt = MGA_REALLOC(mga_chain_text_t, txt, m_txt); }
+			for (k = 0; k < gcs->n_gc; ++k) {
+				txt[k].cg = txt[k].ds = txt[k].vt = 0;
+				if ((gcs->gc[k].id != gcs->gc[k].parent && !(bt->opt.flag & MG_M_PRINT_2ND)) || gcs->gc[k].cnt == 0) continue;
+				txt[k].vt = bt->vert_dev + bt->vert_off[l], txt[k].vt_len = (int32_t)(bt->vert_off[l + 1] - bt->vert_off[l]), ++l;
 			}
 			tx = txt;
 		}

@@ -41,6 +41,8 @@ struct mga_batch_s {
 	const mga_txt_res_t *txt_res; /* text-mode results, global chain order */
 	const char *txt_pool;
 	const char *gaf_dev; int64_t gaf_dev_len; /* the chunk's GAF lines as the device wrote them (k_gaf.hip), read order, back to back; NULL: the host formats */
+	const char *vert_dev; const int64_t *vert_off, *vert_line0; /* a job without -c: the per-vertex lines (-S / --write-mz) of the chunk's printed chains as the device wrote them
+	                         * (k_gaf_vert.hip): chain number l of the chunk at vert_dev + vert_off[l], read i's first printed chain is number vert_line0[i]; NULL: the host formats them */
 	/* stage-1 inputs, valid during mga_batch_chain() only */
 	const int32_t *n_mz, *rep_len, *mini_pos, *nu, *nb;
 	const int64_t *mini_off, *a_off;

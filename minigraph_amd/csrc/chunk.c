@@ -131,6 +131,41 @@ static int64_t gaf_lines_build(const mga_batch_t *b, int n, mga_gaf_line_t *line
 	return nl;
 }
 
+/* ... and where the per-vertex lines of -S / --write-mz find their inputs (k_gaf_vert.hip): one record per line of gaf_lines_build(), in its order.  The chains of a read that
+ * was chained on the device are read where k_gchain left them (src 0: the record pools, at the read's header offsets).  The mg_llchain_t records and the anchors of every other
+ * read with a printed chain are staged back to back (src 1) for one upload; a first call with vl == NULL only sizes the stage.  only: a job without -c, whose lines the host
+ * formats: no line records and no plan exist, so the records are those of the chains the writer prints (format.c:135-136), none for an unmapped read, and line0[i] (with vl) is
+ * the number of read i's first one.  *n_lines: records; returns the number of vertex lines. */
+static int64_t gaf_vlines_build(const mga_batch_t *b, int n, mga_gaf_vline_t *vl, mg_llchain_t *stage_lc, mg128_t *stage_a, int64_t *n_stage_lc, int64_t *n_stage_a, int only, int64_t *line0,
+								int64_t *n_lines)
+{
+	int64_t nl = 0, slc = 0, sa = 0, n_vert = 0;
+	int i, k;
+	for (i = 0; i < n; ++i) {
+		const mg_gchains_t *gcs = b->gcs[i];
+		const read_plan_t *pl = &b->plan[i];
+		const int dev = b->gc_hdr && b->gc_hdr[i].status == 0;
+		int any = 0;
+		if (only && vl) line0[i] = nl;
+		if (gcs == 0 || gcs->n_gc == 0) {
+			if (!only && (b->opt.flag & MG_M_SHOW_UNMAP)) { if (vl) memset(&vl[nl], 0, sizeof *vl); ++nl; }
+			continue;
+		}
+		for (k = 0; k < gcs->n_gc; ++k) {
+			const mg_gchain_t *p = &gcs->gc[k];
+			if (only ? (p->id != p->parent && !(b->opt.flag & MG_M_PRINT_2ND)) || p->cnt == 0 : pl->chain_id[k] < 0) continue;
+			if (vl) vl[nl].lc_beg = (dev ? b->gc_hdr[i].lc_off : slc) + p->off, vl[nl].a_base = dev ? b->gc_hdr[i].a_off : sa, vl[nl].n_lc = p->cnt, vl[nl].src = !dev;
+			++nl, n_vert += p->cnt, any = 1;
+		}
+		if (!dev && any) {
+			if (vl) { memcpy(stage_lc + slc, gcs->lc, (size_t)gcs->n_lc * sizeof(mg_llchain_t)); memcpy(stage_a + sa, gcs->a, (size_t)gcs->n_a * 16); }
+			slc += gcs->n_lc, sa += gcs->n_a;
+		}
+	}
+	*n_stage_lc = slc, *n_stage_a = sa, *n_lines = nl;
+	return n_vert;
+}
+
 /* the wide launcher's answer, as chunk_gaf_dev() takes it: 0 the device's lines stand; 1 a line's bytes do not fit line_len's int32: the chunk goes to the host writer
  * as it did before there was a wide form; -1 an error */
 int mga_gaf_wide_route(int rc) { return rc == 0 ? 0 : rc == MGA_GAF_WIDE_TOO_LONG ? 1 : -1; }
@@ -140,6 +175,17 @@ void mga_gaf_wide_stats(int64_t out[2], int reset)
 {
 	int i;
 	for (i = 0; i < 2; ++i) { out[i] = __atomic_load_n(&g_gaf_wide_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_gaf_wide_stats[i], 0, __ATOMIC_RELAXED); }
+}
+
+static int64_t g_gaf_vert_stats[3]; /* since the last reset: per-vertex lines (-S / --write-mz) the device wrote (k_gaf_vert.hip), chunks handed to the host writer for a div on a rounding boundary, for a line's size or wide routing */
+void mga_gaf_vert_count(int64_t lines, int64_t div_back, int64_t size_back)
+{
+	__atomic_fetch_add(&g_gaf_vert_stats[0], lines, __ATOMIC_RELAXED); __atomic_fetch_add(&g_gaf_vert_stats[1], div_back, __ATOMIC_RELAXED); __atomic_fetch_add(&g_gaf_vert_stats[2], size_back, __ATOMIC_RELAXED);
+}
+void mga_gaf_vert_stats(int64_t out[3], int reset)
+{
+	int i;
+	for (i = 0; i < 3; ++i) { out[i] = __atomic_load_n(&g_gaf_vert_stats[i], __ATOMIC_RELAXED); if (reset) __atomic_store_n(&g_gaf_vert_stats[i], 0, __ATOMIC_RELAXED); }
 }
 
 typedef struct { char *dst; const char *src; int64_t bytes; int T; } pcopy_t;
@@ -169,6 +215,7 @@ typedef struct {
 	int gaf_direct;     /* MGA_GAF_DIRECT=0: a chunk's lines always go through its pieces, never straight to their place in the job's output */
 	int dev_gaf_wide;   /* MGA_DEV_GAF_WIDE=1: the lines of chromosome-scale chains (-x asm) are written on the device as well, a workgroup per line (k_gaf_wide.hip); otherwise by the host writer */
 	int gaf_wide_min;   /* MGA_GAF_WIDE_MIN: plan items + CIGAR operators per chain from which a chunk's chains count as chromosome-scale (default 32768; the tests lower it) */
+	int dev_gaf_vert;   /* MGA_DEV_GAF_VERT=0: a job with -S / --write-mz keeps the host writer; otherwise its per-vertex lines are written on the device too (k_gaf_vert.hip) */
 } chunk_knobs_t;
 
 static void chunk_knobs_read(chunk_knobs_t *k)
@@ -181,6 +228,7 @@ static void chunk_knobs_read(chunk_knobs_t *k)
 	k->dev_lcdp = env_int("MGA_DEV_LCDP", 0);
 	k->txt_tight = env_int("MGA_TXT_TIGHT", 0), k->dev_gaf = env_int("MGA_DEV_GAF", 1), k->gaf_direct = env_int("MGA_GAF_DIRECT", 1);
 	k->dev_gaf_wide = env_int("MGA_DEV_GAF_WIDE", 0), k->gaf_wide_min = env_int("MGA_GAF_WIDE_MIN", 32768);
+	k->dev_gaf_vert = env_int("MGA_DEV_GAF_VERT", 1);
 }
 
 typedef struct { /* one run of the stage sequence: a stack object of map_chunk() */
@@ -212,6 +260,13 @@ typedef struct { /* one run of the stage sequence: a stack object of map_chunk()
 
 static void chunk_token_acquire(chunk_t *c, gpu_token_t *t) { token_acquire(t); c->held = t; }
 static void chunk_token_release(chunk_t *c) { if (c->held) { token_release(c->held); c->held = 0; } }
+
+/* may the device write the per-vertex lines of this chunk (-S / --write-mz, k_gaf_vert.hip)?  What is known before the chunk has chains: chunk_gaf_dev() adds the routing of
+ * chromosome-scale chains, and the kernel may still hand the chunk back (a div on a rounding boundary, a line past 2^31 bytes) */
+static int gaf_vert_dev(const chunk_t *c)
+{
+	return c->want_text && c->in.gaf_part != 0 && c->in.gi->B->dev.d_gaf_seg != 0 && !(c->in.opt->flag & MG_M_FRAG_MERGE) && !(mg_dbg_flag & 0x8) && c->k.dev_gaf && c->k.dev_gaf_vert;
+}
 
 /* a stage is over: its interval goes to `acc` and to the MGA_DEBUG_PIPE log */
 static void chunk_lap(chunk_t *c, const char *what, double *acc)
@@ -539,7 +594,8 @@ static int chunk_gchain_dev(chunk_t *c)
 	c->h_gchdr_p = (mga_gc_hdr_t*)P->h_gchdr.p;
 	CK(mga_d2h_s(sc, c->h_gchdr_p, P->gchdr.p, (size_t)n * sizeof(mga_gc_hdr_t)));
 	CK(mga_d2h_s(sc, P->h_gcpool.p, P->gcpool.p, (size_t)ctl[1] * rec)); CK(mga_d2h_s(sc, P->h_lcpool.p, P->lcpool.p, (size_t)ctl[2] * sizeof(mg_llchain_t)));
-	c->need_a = (!c->dev_plan && !c->in.cov) || (mg_dbg_flag & 0x8) || (opt->flag & MG_M_WRITE_LCHAIN); /* with the gap list made on the device, only the per-vertex lines (-S / --write-mz) read anchors on the host */
+	c->need_a = (!c->dev_plan && !c->in.cov) || (mg_dbg_flag & 0x8) || ((opt->flag & MG_M_WRITE_LCHAIN) && !gaf_vert_dev(c)); /* with the gap list made on the device, only the per-vertex lines (-S / --write-mz) read anchors
+	                                                      * on the host, and only where the host writes them (a chunk the device hands back fetches them then: gaf_vert_anchors_down) */
 	if (c->need_a) CK(mga_d2h_s(sc, P->h_apool.p, P->apool.p, (size_t)ctl[6] * 16));
 	CK(mga_ssync(sc)); /* (h_nu / h_nb / h_rflag arrived with the first sync) */
 	for (i = 0; i < n; ++i) /* the few reads whose rescue k_lchain left to the host tree: their chains, anchors and minimizer positions come down for the host path */
@@ -731,19 +787,41 @@ static int chunk_text(chunk_t *c)
 }
 
 /* Round 6: the whole LINES are written on the device (k_gaf.hip) -- name, coordinates, path column, tags in front of the two strings, every line at its place in
- * the chunk's text -- unless the job asks for what only the host's writer prints (per-vertex lines of -S / --write-mz).  Chromosome-scale chains (their walks have 10^5
+ * the chunk's text; under -S / --write-mz the per-vertex lines follow each chain's line (k_gaf_vert.hip: its counting pass runs between k_gaf's and the scan, its writing pass
+ * behind k_gaf's; a div on a rounding boundary or a line past 2^31 bytes hands the chunk to the host writer, as do --frag, mg_dbg_flag & 8 and MGA_DEV_GAF_VERT=0).  Chromosome-scale chains (their walks have 10^5
  * vertices: one wavefront per line would fold them alone) take the workgroup form (k_gaf_wide.hip) under MGA_DEV_GAF_WIDE=1; without it, or when a line's bytes do not fit
  * an int32, the strings come down for the host's writer.  Either way the text results land here. */
+static int gaf_vert_anchors_down(chunk_t *c) /* a chunk whose per-vertex lines the device was to write goes to the host writer after all: the device-made chains get their anchors now */
+{
+	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc;
+	int i;
+	CK(mga_d2h_s(sc, P->h_apool.p, P->apool.p, (size_t)c->ctl[6] * 16)); CK(mga_ssync(sc));
+	for (i = 0; i < c->in.n; ++i) {
+		const mga_gc_hdr_t *h = &c->h_gchdr_p[i];
+		mg_gchains_t *gs = c->b->gcs[i];
+		if (h->status != 0 || gs == 0 || gs->n_gc == 0 || h->n_a <= 0) continue;
+		gs->a = MGA_REALLOC(mg128_t, gs->a, h->n_a);
+		memcpy(gs->a, (const mg128_t*)P->h_apool.p + h->a_off, (size_t)h->n_a * 16);
+		gs->n_a = h->n_a;
+	}
+	return 0;
+}
+
 static int chunk_gaf_dev(chunk_t *c)
 {
 	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc; struct mg_idx_bucket_s *B = c->in.gi->B; const mg_mapopt_t *opt = c->in.opt; mga_batch_t *b = c->b; const int n = c->in.n; const char **qnames = c->in.qnames;
 	const int64_t n_chain = c->n_chain;
-	int64_t n_lines = -1, k;
-	int i, wide = 0;
-	if (c->in.gaf_part && B->dev.d_gaf_seg != 0 && !(opt->flag & (MG_M_WRITE_LCHAIN | MG_M_WRITE_MZ | MG_M_FRAG_MERGE)) && !(mg_dbg_flag & 0x8) && n_chain > 0 &&
-		((wide = (c->n_item + c->n_ops) / n_chain >= c->k.gaf_wide_min) == 0 || c->k.dev_gaf_wide) && n_chain < 0x7fffffffLL && c->k.dev_gaf) {
-		CK(mga_hbuf_reserve(&P->h_gline, (size_t)(n_chain + n) * sizeof(mga_gaf_line_t) + 64));
-		n_lines = gaf_lines_build(b, n, (mga_gaf_line_t*)P->h_gline.p);
+	const int vflag = (opt->flag & (MG_M_WRITE_LCHAIN | MG_M_WRITE_MZ)) != 0; /* the job asks for per-vertex lines (printed under MG_M_WRITE_LCHAIN: gaf.c) */
+	int64_t n_lines = -1, n_vlines = 0, tot_b = 0, k;
+	int i, wide = 0, vert = 0;
+	if (c->in.gaf_part && B->dev.d_gaf_seg != 0 && !(opt->flag & MG_M_FRAG_MERGE) && (!vflag || gaf_vert_dev(c)) && !(mg_dbg_flag & 0x8) && n_chain > 0 && n_chain < 0x7fffffffLL && c->k.dev_gaf) {
+		wide = (c->n_item + c->n_ops) / n_chain >= c->k.gaf_wide_min;
+		if (wide && vflag) mga_gaf_vert_count(0, 0, 1); /* chromosome-scale chains with per-vertex lines: the host writer, as before */
+		else if (!wide || c->k.dev_gaf_wide) {
+			CK(mga_hbuf_reserve(&P->h_gline, (size_t)(n_chain + n) * sizeof(mga_gaf_line_t) + 64));
+			n_lines = gaf_lines_build(b, n, (mga_gaf_line_t*)P->h_gline.p);
+			vert = n_lines > 0 && (opt->flag & MG_M_WRITE_LCHAIN) != 0;
+		}
 	}
 	if (n_lines > 0) { /* line records and names up, then count -> scan -> write */
 		int64_t qn_bytes = 0, *qo;
@@ -764,23 +842,92 @@ static int chunk_gaf_dev(chunk_t *c)
 		} else
 			CK(mga_dev_gaf(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
 						   (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, 0, 0));
+		if (vert) { /* the per-vertex lines behind each chain's line: their records up (one pinned staging copy), their bytes added to the lines' lengths */
+			int64_t n_slc = 0, n_sa = 0, n_vrec = 0;
+			char *hs;
+			n_vlines = gaf_vlines_build(b, n, 0, 0, 0, &n_slc, &n_sa, 0, 0, &n_vrec);
+			CK(mga_hbuf_reserve(&P->h_gvline, (size_t)n_lines * sizeof(mga_gaf_vline_t) + 64)); CK(mga_hbuf_reserve(&P->h_gvstage, (size_t)n_sa * 16 + (size_t)n_slc * sizeof(mg_llchain_t) + 64));
+			hs = (char*)P->h_gvstage.p; /* anchors | records */
+			(void)gaf_vlines_build(b, n, (mga_gaf_vline_t*)P->h_gvline.p, (mg_llchain_t*)(hs + n_sa * 16), (mg128_t*)hs, &n_slc, &n_sa, 0, 0, &n_vrec);
+			CK(mga_dbuf_reserve(&P->gv_line, (size_t)n_lines * sizeof(mga_gaf_vline_t) + 64)); CK(mga_dbuf_reserve(&P->gv_lc, (size_t)n_slc * sizeof(mg_llchain_t) + 64));
+			CK(mga_dbuf_reserve(&P->gv_a, (size_t)n_sa * 16 + 64)); CK(mga_dbuf_reserve(&P->g_hdr, (size_t)(n_lines + 1) * 4)); CK(mga_dbuf_reserve(&P->gv_hb, 64));
+			CK(mga_h2d_s(sc, P->gv_line.p, P->h_gvline.p, (size_t)n_lines * sizeof(mga_gaf_vline_t)));
+			if (n_sa > 0) CK(mga_h2d_s(sc, P->gv_a.p, hs, (size_t)n_sa * 16));
+			if (n_slc > 0) CK(mga_h2d_s(sc, P->gv_lc.p, hs + n_sa * 16, (size_t)n_slc * sizeof(mg_llchain_t)));
+			CK(mga_dmemset_s(sc, P->gv_hb.p, 0, 8));
+			CK(mga_dev_gaf_vert(sc, &B->dev, (int)n_lines, (const mga_gaf_vline_t*)P->gv_line.p, (const mg_llchain_t*)P->lcpool.p, (const mg128_t*)P->apool.p, (const mg_llchain_t*)P->gv_lc.p,
+								(const mg128_t*)P->gv_a.p, opt->flag, (int32_t*)P->g_len.p, (int32_t*)P->g_hdr.p, (int32_t*)P->gv_hb.p, 0, 0));
+		}
 	}
 	if (n_lines > 0) {
-		int64_t tot_b = 0;
+		int32_t hb[2] = { 0, 0 };
 		CK(mga_dev_scan_i32_to_i64(sc, (const int32_t*)P->g_len.p, n_lines, (int64_t*)P->g_off.p));
+		if (vert) CK(mga_d2h_s(sc, hb, P->gv_hb.p, 8));
 		CK(mga_d2h_s(sc, &tot_b, (int64_t*)P->g_off.p + n_lines, 8)); CK(mga_ssync(sc));
+		if (hb[0] || hb[1]) { mga_gaf_vert_count(0, hb[0] != 0, hb[0] == 0); n_lines = -1; } /* a div the host has to print, or a line past 2^31 bytes: the chunk goes to the host writer */
+	}
+	if (n_lines > 0) {
 		CK(mga_dbuf_reserve(&P->g_out, (size_t)tot_b + 64)); CK(mga_hbuf_reserve(&P->h_gout, (size_t)tot_b + 64));
 		CK((wide ? mga_dev_gaf_wide : mga_dev_gaf)(sc, &B->dev, (int)n_lines, (const mga_gaf_line_t*)P->g_line.p, (const char*)P->g_qn.p, (const int64_t*)P->g_qoff.p, opt->flag, (const mga_txt_chain_t*)P->chain.p,
 					   (const uint32_t*)P->vert.p, (const mga_txt_res_t*)P->txtres.p, (const char*)P->txtpool.p, (int32_t*)P->g_len.p, (const int64_t*)P->g_off.p, (char*)P->g_out.p));
 		if (wide) __atomic_fetch_add(&g_gaf_wide_stats[0], n_lines, __ATOMIC_RELAXED);
+		if (vert) { /* ... and every chain's vertex lines behind its header */
+			CK(mga_dev_gaf_vert(sc, &B->dev, (int)n_lines, (const mga_gaf_vline_t*)P->gv_line.p, (const mg_llchain_t*)P->lcpool.p, (const mg128_t*)P->apool.p, (const mg_llchain_t*)P->gv_lc.p,
+								(const mg128_t*)P->gv_a.p, opt->flag, (int32_t*)P->g_len.p, (int32_t*)P->g_hdr.p, (int32_t*)P->gv_hb.p, (const int64_t*)P->g_off.p, (char*)P->g_out.p));
+			mga_gaf_vert_count(n_vlines, 0, 0);
+		}
 		if (tot_b > 0) CK(mga_d2h_s(sc, P->h_gout.p, P->g_out.p, (size_t)tot_b));
 		b->gaf_dev = (const char*)P->h_gout.p, b->gaf_dev_len = tot_b;
 	} else if (n_lines == 0) b->gaf_dev = "", b->gaf_dev_len = 0; /* (nothing of this chunk is printed) */
-	else { CK(mga_hbuf_reserve(&P->h_txtpool, (size_t)c->txt_used + 16)); CK(mga_d2h_s(sc, P->h_txtpool.p, P->txtpool.p, (size_t)c->txt_used)); }
+	else {
+		CK(mga_hbuf_reserve(&P->h_txtpool, (size_t)c->txt_used + 16)); CK(mga_d2h_s(sc, P->h_txtpool.p, P->txtpool.p, (size_t)c->txt_used));
+		if ((opt->flag & MG_M_WRITE_LCHAIN) && c->dev_gc && !c->need_a) CK(gaf_vert_anchors_down(c)); /* the host writes the per-vertex lines after all */
+	}
 	CK(mga_ssync(sc));
 	for (k = 0; k < n_chain; ++k)
 		if (((const mga_txt_res_t*)P->h_txtres.p)[k].status != 0) { mga_set_error("text kernel: stitched CIGAR inconsistent with the chain coordinates (galign.c:140), chain %ld", (long)k); return -1; }
 	b->txt_res = (const mga_txt_res_t*)P->h_txtres.p, b->txt_pool = b->gaf_dev ? 0 : (const char*)P->h_txtpool.p;
+	return 0;
+}
+
+/* A job without -c: the host formats every chain's line (the line kernel prints lines with cg:Z / ds:Z only), but the per-vertex lines of -S / --write-mz still come from the
+ * device: k_gaf_vert.hip over the printed chains with header lengths of 0, count -> scan -> write, and the writer copies each chain's block behind its line (gaf.c: vt).  The
+ * anchors are on the host in this mode anyway, so a hand-back (a div on a rounding boundary, a block past 2^31 bytes) simply leaves the lines to the writer.  Chunks of -x asm and
+ * of ultra-long reads (walks of 10^5 vertices) stay with the host writer, like their lines do under -c. */
+static int chunk_gaf_vert_only(chunk_t *c)
+{
+	pipe_ctx_t *P = c->P; mga_sctx_t *sc = P->sc; struct mg_idx_bucket_s *B = c->in.gi->B; const mg_mapopt_t *opt = c->in.opt; mga_batch_t *b = c->b; const int n = c->in.n;
+	int64_t n_rec = 0, n_vlines, n_slc = 0, n_sa = 0, tot_b = 0, *line0, *off;
+	int32_t hb[2] = { 0, 0 };
+	char *hs;
+	if (!(opt->flag & MG_M_WRITE_LCHAIN) || (opt->flag & (MG_M_CIGAR | MG_M_FRAG_MERGE)) || c->in.gaf_part == 0 || B->dev.d_gaf_seg == 0 || (mg_dbg_flag & 0x8) || !c->k.dev_gaf || !c->k.dev_gaf_vert) return 0;
+	n_vlines = gaf_vlines_build(b, n, 0, 0, 0, &n_slc, &n_sa, 1, 0, &n_rec);
+	if (n_rec == 0) return 0;
+	if (c->is_rmq || c->chunk_long || n_rec >= 0x7fffffffLL) { mga_gaf_vert_count(0, 0, 1); return 0; }
+	CK(mga_hbuf_reserve(&P->h_gvline, (size_t)n_rec * sizeof(mga_gaf_vline_t) + (size_t)(n + 1) * 8 + (size_t)(n_rec + 1) * 8 + 64));
+	CK(mga_hbuf_reserve(&P->h_gvstage, (size_t)n_sa * 16 + (size_t)n_slc * sizeof(mg_llchain_t) + 64));
+	line0 = (int64_t*)((mga_gaf_vline_t*)P->h_gvline.p + n_rec), off = line0 + n + 1; /* records | first record of each read | the blocks' offsets */
+	hs = (char*)P->h_gvstage.p; /* anchors | records */
+	(void)gaf_vlines_build(b, n, (mga_gaf_vline_t*)P->h_gvline.p, (mg_llchain_t*)(hs + n_sa * 16), (mg128_t*)hs, &n_slc, &n_sa, 1, line0, &n_rec);
+	CK(mga_dbuf_reserve(&P->gv_line, (size_t)n_rec * sizeof(mga_gaf_vline_t) + 64)); CK(mga_dbuf_reserve(&P->gv_lc, (size_t)n_slc * sizeof(mg_llchain_t) + 64)); CK(mga_dbuf_reserve(&P->gv_a, (size_t)n_sa * 16 + 64));
+	CK(mga_dbuf_reserve(&P->g_hdr, (size_t)(n_rec + 1) * 4)); CK(mga_dbuf_reserve(&P->gv_hb, 64)); CK(mga_dbuf_reserve(&P->g_len, (size_t)(n_rec + 1) * 4)); CK(mga_dbuf_reserve(&P->g_off, (size_t)(n_rec + 2) * 8));
+	CK(mga_h2d_s(sc, P->gv_line.p, P->h_gvline.p, (size_t)n_rec * sizeof(mga_gaf_vline_t)));
+	if (n_sa > 0) CK(mga_h2d_s(sc, P->gv_a.p, hs, (size_t)n_sa * 16));
+	if (n_slc > 0) CK(mga_h2d_s(sc, P->gv_lc.p, hs + n_sa * 16, (size_t)n_slc * sizeof(mg_llchain_t)));
+	CK(mga_dmemset_s(sc, P->gv_hb.p, 0, 8)); CK(mga_dmemset_s(sc, P->g_len.p, 0, (size_t)(n_rec + 1) * 4)); /* (no headers: every block starts at its offset) */
+	CK(mga_dev_gaf_vert(sc, &B->dev, (int)n_rec, (const mga_gaf_vline_t*)P->gv_line.p, (const mg_llchain_t*)P->lcpool.p, (const mg128_t*)P->apool.p, (const mg_llchain_t*)P->gv_lc.p,
+						(const mg128_t*)P->gv_a.p, opt->flag, (int32_t*)P->g_len.p, (int32_t*)P->g_hdr.p, (int32_t*)P->gv_hb.p, 0, 0));
+	CK(mga_dev_scan_i32_to_i64(sc, (const int32_t*)P->g_len.p, n_rec, (int64_t*)P->g_off.p));
+	CK(mga_d2h_s(sc, hb, P->gv_hb.p, 8)); CK(mga_d2h_s(sc, off, P->g_off.p, (size_t)(n_rec + 1) * 8)); CK(mga_ssync(sc));
+	if (hb[0] || hb[1]) { mga_gaf_vert_count(0, hb[0] != 0, hb[0] == 0); return 0; }
+	tot_b = off[n_rec];
+	CK(mga_dbuf_reserve(&P->g_out, (size_t)tot_b + 64)); CK(mga_hbuf_reserve(&P->h_gout, (size_t)tot_b + 64));
+	CK(mga_dev_gaf_vert(sc, &B->dev, (int)n_rec, (const mga_gaf_vline_t*)P->gv_line.p, (const mg_llchain_t*)P->lcpool.p, (const mg128_t*)P->apool.p, (const mg_llchain_t*)P->gv_lc.p,
+						(const mg128_t*)P->gv_a.p, opt->flag, (int32_t*)P->g_len.p, (int32_t*)P->g_hdr.p, (int32_t*)P->gv_hb.p, (const int64_t*)P->g_off.p, (char*)P->g_out.p));
+	if (tot_b > 0) CK(mga_d2h_s(sc, P->h_gout.p, P->g_out.p, (size_t)tot_b));
+	CK(mga_ssync(sc));
+	mga_gaf_vert_count(n_vlines, 0, 0);
+	b->vert_dev = (const char*)P->h_gout.p, b->vert_off = off, b->vert_line0 = line0;
 	return 0;
 }
 
@@ -972,7 +1119,7 @@ int map_chunk(pipe_ctx_t *P, const chunk_args_t *a)
 		st->n_wfa += c.dp_prob, st->n_wfa_dev_plan += c.dp_prob, st->wfa_t_bases += c.dp_tb, st->wfa_q_bases += (int64_t)c.ptot[5];
 	}
 	chunk_lap(&c, " wfa", &st->t_wfa);
-	if (chunk_finish(&c) < 0) goto done;
+	if (chunk_finish(&c) < 0 || (!cov && chunk_gaf_vert_only(&c) < 0)) goto done;
 	chunk_lap(&c, " hostpost", &st->t_host_post);
 	if (cov ? chunk_cov(&c) < 0 : chunk_emit(&c) < 0) goto done;
 	if (gaf_part || cov) chunk_lap(&c, cov ? " cov" : " gaf", &st->t_gaf);

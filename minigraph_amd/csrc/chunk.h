@@ -20,15 +20,16 @@ typedef struct { /* one pipeline context: HIP stream + grow-only device and pinn
 			mga_dbuf_t rq_a, rq_f, rq_p, rq_v, rq_t, rq_pri, rq_ys, rq_cut, rq_ord, rq_stat, rq_cnt; /* forward pass of the RMQ chainer on the device (k_rmq.hip), one read at a time */
 			mga_dbuf_t g_line, g_qn, g_qoff, g_len, g_off, g_out; /* whole GAF lines on the device (k_gaf.hip): line records, read names, line lengths / offsets, the text */
 			mga_dbuf_t cv_chain, cv_vert; /* read coverage (k_cov.hip): chain records and walk vertices of the chunk */
+			mga_dbuf_t g_hdr, gv_line, gv_lc, gv_a, gv_hb; /* per-vertex lines of -S / --write-mz (k_gaf_vert.hip): header lengths, per-line records, the host-made chains' records and anchors, hand-back flags */
 		};
-		mga_dbuf_t dall[75];
+		mga_dbuf_t dall[80];
 	};
 	union {
-		struct { mga_hbuf_t h_b, h_u, h_mini, h_tseq, h_prob, h_pool, h_seq, h_ncig, h_cigoff, h_item, h_chain, h_vert, h_txtres, h_txtpool, h_gchdr, h_gcpool, h_lcpool, h_apool, h_plrev, h_ploff, h_lcord, h_rq, h_rqs, h_plsrc, h_gline, h_gqn, h_gout, h_cvchain, h_cvvert; }; /* pinned staging */
-		mga_hbuf_t hall[29];
+		struct { mga_hbuf_t h_b, h_u, h_mini, h_tseq, h_prob, h_pool, h_seq, h_ncig, h_cigoff, h_item, h_chain, h_vert, h_txtres, h_txtpool, h_gchdr, h_gcpool, h_lcpool, h_apool, h_plrev, h_ploff, h_lcord, h_rq, h_rqs, h_plsrc, h_gline, h_gqn, h_gout, h_cvchain, h_cvvert, h_gvline, h_gvstage; }; /* pinned staging */
+		mga_hbuf_t hall[31];
 	};
 } pipe_ctx_t;
-_Static_assert(sizeof(((pipe_ctx_t*)0)->dall) == 75 * sizeof(mga_dbuf_t) && sizeof(((pipe_ctx_t*)0)->hall) == 29 * sizeof(mga_hbuf_t), "pipe_ctx_t: buffer lists out of sync");
+_Static_assert(sizeof(((pipe_ctx_t*)0)->dall) == 80 * sizeof(mga_dbuf_t) && sizeof(((pipe_ctx_t*)0)->hall) == 31 * sizeof(mga_hbuf_t), "pipe_ctx_t: buffer lists out of sync");
 
 MGA_LOCAL void pipe_ctx_free(pipe_ctx_t *P);
 

@@ -1,5 +1,5 @@
 // dev_gaf.h -- what the two forms of the GAF line kernel share (k_gaf.hip: a wavefront per line; k_gaf_wide.hip: a workgroup per line): the name tables of the graph in HBM,
-// the staged formatter of the scalar columns and printf's "%.4f".  Included by those two files only.
+// the staged formatter of the scalar columns and printf's "%.4f".  Included by those two files and by k_gaf_vert.hip (the per-vertex lines of -S / --write-mz) only.
 #ifndef MGA_DEV_GAF_H
 #define MGA_DEV_GAF_H
 
@@ -9,6 +9,10 @@ struct gaf_seg_t { int64_t name_off; int32_t name_len, snid, soff, len; };   // 
 struct gaf_sseq_t { int64_t name_off; int32_t name_len, min, max, rank; };   // per stable sequence (gfa_sseq_t)
 
 #define GAF_STAGE 1024 // bytes of the LDS stage; a token (a number, a tag) is at most 16 bytes, longer strings are copied in pieces
+
+// the decimal text of an unsigned number, for every writer of GAF bytes on the device: its width, then its digits at w[0 .. nd)
+__device__ __forceinline__ int32_t gaf_ndig(uint32_t x) { int32_t nd = 1; for (uint32_t y = x; y >= 10; y /= 10) ++nd; return nd; }
+__device__ __forceinline__ void gaf_put_u(char *w, uint32_t x, int32_t nd) { for (int32_t i = nd - 1; i >= 0; --i) { w[i] = (char)('0' + x % 10); x /= 10; } }
 
 template<bool WRITE> struct gaf_out_t {
 	char *stage;      // LDS
@@ -31,10 +35,9 @@ template<bool WRITE> struct gaf_out_t {
 	__device__ __forceinline__ void lit(const char *s, int32_t len) { room(len); if (WRITE && lane == 0) for (int32_t i = 0; i < len; ++i) stage[n + i] = s[i]; n += len, total += len; }
 	__device__ __forceinline__ void u(uint32_t x)
 	{
-		int32_t nd = 1;
-		for (uint32_t y = x; y >= 10; y /= 10) ++nd;
+		const int32_t nd = gaf_ndig(x);
 		room(nd);
-		if (WRITE && lane == 0) { uint32_t y = x; for (int32_t i = nd - 1; i >= 0; --i) { stage[n + i] = (char)('0' + y % 10); y /= 10; } }
+		if (WRITE && lane == 0) gaf_put_u(stage + n, x, nd);
 		n += nd, total += nd;
 	}
 	__device__ __forceinline__ void d(int32_t x) { if (x < 0) { c('-'); u((uint32_t)-(int64_t)x); } else u((uint32_t)x); }

@@ -269,7 +269,13 @@ void mga_write_gaf_append(kstring_t *s, const gfa_t *g, const mg_gchains_t *gs, 
 		}
 		KS_FITS(s, 1);
 		ks_c(s, '\n');
-		if ((mg_dbg_flag & 0x8) || (flag & MG_M_WRITE_LCHAIN)) { /* one line per vertex of the walk, -S / --write-mz (format.c:252-289) */
+		if (txt && txt[i].vt && (flag & MG_M_WRITE_LCHAIN)) { /* the chain's per-vertex lines as the device wrote them (k_gaf_vert.hip) */
+			ks_room(s, (size_t)txt[i].vt_len);
+			KS_FITS(s, (size_t)txt[i].vt_len);
+			memcpy(s->s + s->l, txt[i].vt, (size_t)txt[i].vt_len);
+			s->l += (unsigned)txt[i].vt_len;
+			KS_TERM(s);
+		} else if ((mg_dbg_flag & 0x8) || (flag & MG_M_WRITE_LCHAIN)) { /* one line per vertex of the walk, -S / --write-mz (format.c:252-289) */
 			for (j = 0; j < p->cnt; ++j) {
 				const mg_llchain_t *lc = &gs->lc[p->off + j];
 				const gfa_seg_t *t = &g->seg[lc->v >> 1];
@@ -305,4 +311,37 @@ void mga_write_gaf_append(kstring_t *s, const gfa_t *g, const mg_gchains_t *gs, 
 			KS_TERM(s);
 		}
 	}
+}
+
+/* the host route of mga_gaf_vert_batch (stage_api.hip): the hand-made chains of every read as an mg_gchains_t over the shared record and anchor arrays, through the writer above
+ * with the text the caller supplies; returns the bytes, *out malloc'ed */
+int64_t mga_gaf_vert_host(const gfa_t *g, int n_reads, const char *qnames, const int64_t *qname_off, const int32_t *qlens, const int64_t *gc_off, const mga_gaf_vchain_t *ch,
+						  const mg_llchain_t *lc, const mg128_t *a, const char *pool, uint64_t flag, char **out)
+{
+	kstring_t s = { 0, 0, 0 };
+	int r;
+	ks_room(&s, 0);
+	for (r = 0; r < n_reads; ++r) {
+		const int32_t n_gc = (int32_t)(gc_off[r + 1] - gc_off[r]);
+		const size_t ql = (size_t)(qname_off[r + 1] - qname_off[r]);
+		char *name = (char*)malloc(ql + 1);
+		mg_gchains_t gs;
+		mga_chain_text_t *txt = (mga_chain_text_t*)calloc(n_gc > 0 ? n_gc : 1, sizeof *txt);
+		int32_t k;
+		memcpy(name, qnames + qname_off[r], ql); name[ql] = 0;
+		memset(&gs, 0, sizeof gs);
+		gs.n_gc = n_gc, gs.lc = (mg_llchain_t*)lc, gs.a = (mg128_t*)a;
+		gs.gc = (mg_gchain_t*)calloc(n_gc > 0 ? n_gc : 1, sizeof(mg_gchain_t));
+		for (k = 0; k < n_gc; ++k) {
+			const mga_gaf_vchain_t *c = &ch[gc_off[r] + k];
+			mg_gchain_t *p = &gs.gc[k];
+			p->id = c->id, p->parent = c->parent, p->off = c->lc_off, p->cnt = c->cnt, p->n_anchor = c->n_anchor, p->score = c->score, p->subsc = c->subsc;
+			p->qs = c->qs, p->qe = c->qe, p->plen = c->plen, p->ps = c->ps, p->pe = c->pe, p->mapq = (uint32_t)c->mapq, p->div = c->div;
+			txt[k].cg = pool + c->txt_off, txt[k].ds = pool + c->txt_off + c->cg_len, txt[k].cg_len = c->cg_len, txt[k].ds_len = c->ds_len, txt[k].mlen = c->mlen, txt[k].blen = c->blen;
+		}
+		mga_write_gaf_append(&s, g, &gs, 1, &qlens[r], name, flag, txt);
+		free(gs.gc); free(txt); free(name);
+	}
+	*out = s.s;
+	return (int64_t)s.l;
 }

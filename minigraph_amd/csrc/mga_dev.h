@@ -246,6 +246,20 @@ int mga_dev_gaf_wide_tile(void);              /* vertices of a tile = threads of
 int32_t mga_gaf_len32_host(int64_t total);    /* a line's 64-bit byte count as the kernel stores it in d_len: the count, or -1 */
 /* chunk.c: what a chunk does with the wide launcher's answer: 0 the device's lines stand, 1 the chunk goes to the host writer, -1 an error */
 int mga_gaf_wide_route(int rc);
+/* the per-vertex lines of -S / --write-mz behind the lines of mga_dev_gaf (k_gaf_vert.hip; format.c:252-289).  One record per line record, in the same order: where the printed
+ * chain's mg_llchain_t records and the anchors of its read lie -- pool `src` (0: graph chaining's record pools in place; 1: what the host threads chained, uploaded), the chain's
+ * first record at lc + lc_beg, anchor `off` of a record at a + a_base + off.  n_lc == 0: no vertex lines (an unmapped read's line).
+ * Pass 1 (d_out == NULL) runs BEHIND mga_dev_gaf's pass 1: d_hdr[i] = d_len[i], then d_len[i] grows by the vertex lines' bytes; d_hb[0] is raised when a div has to be printed by
+ * the host (it lies on a rounding boundary of "%.4f", or the host prints inf / nan), d_hb[1] when a line passes 2^31 bytes (the caller zeroes both).  Pass 2 runs behind
+ * mga_dev_gaf's pass 2 and writes at d_out + d_off[i] + d_hdr[i].  MG_M_WRITE_MZ in `flag` selects the form with the distance lists. */
+typedef struct { int64_t lc_beg, a_base; int32_t n_lc, src; } mga_gaf_vline_t;
+int mga_dev_gaf_vert(mga_sctx_t *sc, const mga_didx_t *ix, int n_lines, const mga_gaf_vline_t *d_vline, const mg_llchain_t *d_lc0, const mg128_t *d_a0,
+					 const mg_llchain_t *d_lc1, const mg128_t *d_a1, uint64_t flag, int32_t *d_len, int32_t *d_hdr, int32_t *d_hb, const int64_t *d_off, char *d_out);
+/* chunk.c: the counters behind mga_gaf_vert_stats(): vertex lines the device wrote, chunks handed to the host writer for a div / for size or wide routing */
+void mga_gaf_vert_count(int64_t lines, int64_t div_back, int64_t size_back);
+/* gaf.c: the host route of mga_gaf_vert_batch (stage_api.hip) */
+int64_t mga_gaf_vert_host(const gfa_t *g, int n_reads, const char *qnames, const int64_t *qname_off, const int32_t *qlens, const int64_t *gc_off, const mga_gaf_vchain_t *ch,
+						  const mg_llchain_t *lc, const mg128_t *a, const char *pool, uint64_t flag, char **out);
 
 /* ---- read coverage on the device (k_cov.hip, cov_core.h): mg_cov_map, cal_cov.c:8-53, as integer sums ----
  * chain records + walk vertices of a chunk are ADDED into d_seg_bases[n_seg] / d_link_cnt[n_arc] / d_cnt[MGA_COV_N_CNT] (the job's accumulators: zeroed by the caller, once) */

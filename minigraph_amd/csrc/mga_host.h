@@ -117,7 +117,7 @@ int mga_cov_job_close(mga_cov_job_t *J, int64_t *seg_bases, int64_t *link_cnt, m
 void mga_cov_read_host(const cov_graph_t *G, const mg_gchains_t *gt, int32_t min_mapq, int32_t min_blen, int64_t *seg_bases, int64_t *link_cnt, int64_t *cnt);
 void mga_stream_set_cov(mga_stream_t *S, mga_cov_job_t *J); /* the chunks of the batches submitted from now on end in chunk_cov() (chunk.c); NULL: GAF / chains again */
 
-typedef struct { const char *cg, *ds; int32_t cg_len, ds_len, mlen, blen; } mga_chain_text_t; /* cg == NULL: format from the chain itself */
+typedef struct { const char *cg, *ds; int32_t cg_len, ds_len, mlen, blen; const char *vt; int32_t vt_len; } mga_chain_text_t; /* cg == NULL: format from the chain itself; vt != NULL: the chain's per-vertex lines (-S / --write-mz) as the device wrote them */
 #define MGA_KS_WINDOW 0xffffffffu /* kstring_t::m of a window into another buffer: never reallocated, never NUL-terminated (gaf.c) */
 void mga_gaf_window_limit(size_t bytes); /* the calling thread's next window holds this many bytes: a write past it aborts before it happens (gaf.c) */
 void mga_write_gaf_append(kstring_t *s, const gfa_t *g, const mg_gchains_t *gs, int32_t n_seg, const int32_t *qlens, const char *qname, uint64_t flag,

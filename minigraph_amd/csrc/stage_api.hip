@@ -255,6 +255,93 @@ extern "C" int mga_gaf_lines_batch(const mg_idx_t *gi, int n_lines, const void *
 	return 0;
 }
 
+// The lines of -S / --write-mz as a stage: hand-made chains -> the records a chunk hands to mga_dev_gaf and mga_dev_gaf_vert (lines as gaf_lines_build() lists them, walks from
+// the records' vertices, every chain's records and anchors in pool 1) -> count, count, scan, write, write as chunk_gaf_dev() runs them; a hand-back ends in the host writer.
+// tests/test_gpu_gaf_vert.py
+extern "C" int mga_gaf_vert_batch(const mg_idx_t *gi, int n_reads, const char *qnames, const int64_t *qname_off, const int32_t *qlens, const int64_t *gc_off, const mga_gaf_vchain_t *ch,
+								  int64_t n_lc, const mg_llchain_t *lc, int64_t n_a, const mg128_t *a, const char *pool, int64_t pool_len, uint64_t flag, int route, char **out, int64_t *out_len)
+{
+	*out = 0, *out_len = 0;
+	if (n_reads < 0 || n_lc < 0 || n_a < 0 || pool_len < 0 || (route != 0 && route != 1)) { mga_set_error("gaf_vert_batch: bad arguments"); return -1; }
+	const uint32_t n_vtx = gfa_n_vtx(gi->g);
+	const int64_t n_gc = n_reads > 0 ? gc_off[n_reads] : 0;
+	for (int r = 0; r < n_reads; ++r)
+		if (qname_off[r] < 0 || qname_off[r + 1] < qname_off[r] || gc_off[r] < 0 || gc_off[r + 1] < gc_off[r]) { mga_set_error("gaf_vert_batch: the offsets do not ascend"); return -1; }
+	for (int64_t i = 0; i < n_gc; ++i) // both writers trust the records
+		if (ch[i].cnt < 0 || ch[i].lc_off < 0 || (int64_t)ch[i].lc_off + ch[i].cnt > n_lc || ch[i].cg_len < 0 || ch[i].ds_len < 0 || ch[i].txt_off < 0 || ch[i].txt_off + ch[i].cg_len + ch[i].ds_len > pool_len) {
+			mga_set_error("gaf_vert_batch: chain %ld points outside the records or the text pool", (long)i); return -1;
+		}
+	for (int64_t i = 0; i < n_lc; ++i)
+		if (lc[i].v >= n_vtx || lc[i].cnt < 0 || lc[i].off < 0 || (int64_t)lc[i].off + lc[i].cnt > n_a) { mga_set_error("gaf_vert_batch: record %ld names a vertex or anchors that are not there", (long)i); return -1; }
+	if (route == 1) { *out_len = mga_gaf_vert_host(gi->g, n_reads, qnames, qname_off, qlens, gc_off, ch, lc, a, pool, flag, out); return 0; }
+	if (mga_dev_init() < 0) return -1;
+	mga_sctx_t *SC = mga_sctx_default();
+	if (SC == 0) return -1;
+	const mga_didx_t *ix = &((const mg_idx_bucket_s_view*)gi->B)->dev;
+	std::vector<mga_gaf_line_t> ln;
+	std::vector<mga_gaf_vline_t> vl;
+	std::vector<mga_txt_chain_t> tc;
+	std::vector<mga_txt_res_t> tr;
+	std::vector<uint32_t> vert;
+	int64_t n_vlines = 0;
+	for (int r = 0; r < n_reads; ++r) {
+		if (gc_off[r + 1] == gc_off[r]) {
+			if (flag & MG_M_SHOW_UNMAP) { mga_gaf_line_t l; memset(&l, 0, sizeof l); l.read = r, l.chain = -1, l.qlen = qlens[r]; ln.push_back(l); mga_gaf_vline_t v; memset(&v, 0, sizeof v); vl.push_back(v); }
+			continue;
+		}
+		for (int64_t i = gc_off[r]; i < gc_off[r + 1]; ++i) {
+			const mga_gaf_vchain_t &c = ch[i];
+			if ((c.id != c.parent && !(flag & MG_M_PRINT_2ND)) || c.cnt == 0) continue; // not printed (format.c:135-136)
+			mga_gaf_line_t l; mga_gaf_vline_t v; mga_txt_chain_t t; mga_txt_res_t s;
+			memset(&l, 0, sizeof l); memset(&t, 0, sizeof t); memset(&s, 0, sizeof s);
+			l.read = r, l.chain = (int32_t)tc.size(), l.qlen = qlens[r], l.qs = c.qs, l.qe = c.qe, l.plen = c.plen, l.ps = c.ps, l.pe = c.pe, l.mapq = c.mapq, l.n_anchor = c.n_anchor;
+			l.score = c.score, l.subsc = c.subsc, l.primary = c.id == c.parent, l.div = c.div;
+			t.vert_beg = (int64_t)vert.size(), t.vert_cnt = c.cnt;
+			for (int32_t j = 0; j < c.cnt; ++j) vert.push_back(lc[c.lc_off + j].v);
+			s.txt_off = c.txt_off, s.cg_len = c.cg_len, s.ds_len = c.ds_len, s.mlen = c.mlen, s.blen = c.blen;
+			v.lc_beg = c.lc_off, v.a_base = 0, v.n_lc = c.cnt, v.src = 1;
+			ln.push_back(l); vl.push_back(v); tc.push_back(t); tr.push_back(s);
+			n_vlines += c.cnt;
+		}
+	}
+	const int n_lines = (int)ln.size();
+	if (n_lines == 0) { *out = (char*)calloc(1, 1); return 0; }
+	if (!(flag & MG_M_WRITE_LCHAIN)) n_vlines = 0;
+	const int64_t qn_bytes = qname_off[n_reads];
+	const size_t n_chain = tc.size();
+	dptr d_line, d_vl, d_qn, d_qoff, d_chain, d_vert, d_tres, d_pool, d_lc, d_a, d_len, d_hdr, d_hb, d_off, d_out;
+	if (!d_line.alloc((size_t)n_lines * sizeof ln[0]) || !d_vl.alloc((size_t)n_lines * sizeof vl[0]) || !d_qn.alloc((size_t)qn_bytes + 64) || !d_qoff.alloc((size_t)(n_reads + 1) * 8) ||
+		!d_chain.alloc((n_chain + 1) * sizeof tc[0]) || !d_vert.alloc(vert.size() * 4 + 16) || !d_tres.alloc((n_chain + 1) * sizeof tr[0]) || !d_pool.alloc((size_t)pool_len + 64) ||
+		!d_lc.alloc((size_t)n_lc * sizeof lc[0] + 64) || !d_a.alloc((size_t)n_a * 16 + 64) || !d_len.alloc((size_t)(n_lines + 1) * 4) || !d_hdr.alloc((size_t)(n_lines + 1) * 4) || !d_hb.alloc(64) ||
+		!d_off.alloc((size_t)(n_lines + 2) * 8)) return -1;
+	if (mga_h2d(d_line.p, ln.data(), (size_t)n_lines * sizeof ln[0]) < 0 || mga_h2d(d_vl.p, vl.data(), (size_t)n_lines * sizeof vl[0]) < 0 || (qn_bytes > 0 && mga_h2d(d_qn.p, qnames, (size_t)qn_bytes) < 0) ||
+		mga_h2d(d_qoff.p, qname_off, (size_t)(n_reads + 1) * 8) < 0 || (n_chain > 0 && (mga_h2d(d_chain.p, tc.data(), n_chain * sizeof tc[0]) < 0 || mga_h2d(d_tres.p, tr.data(), n_chain * sizeof tr[0]) < 0)) ||
+		(!vert.empty() && mga_h2d(d_vert.p, vert.data(), vert.size() * 4) < 0) || (pool_len > 0 && mga_h2d(d_pool.p, pool, (size_t)pool_len) < 0) ||
+		(n_lc > 0 && mga_h2d(d_lc.p, lc, (size_t)n_lc * sizeof lc[0]) < 0) || (n_a > 0 && mga_h2d(d_a.p, a, (size_t)n_a * 16) < 0) || mga_dmemset_s(SC, d_hb.p, 0, 8) < 0) return -1;
+	auto lines = [&](const int64_t *off, char *dst) {
+		if (mga_dev_gaf(SC, ix, n_lines, d_line.as<mga_gaf_line_t>(), d_qn.as<char>(), d_qoff.as<int64_t>(), flag, d_chain.as<mga_txt_chain_t>(), d_vert.as<uint32_t>(), d_tres.as<mga_txt_res_t>(),
+						d_pool.as<char>(), d_len.as<int32_t>(), off, dst) < 0) return -1;
+		if (!(flag & MG_M_WRITE_LCHAIN)) return 0;
+		return mga_dev_gaf_vert(SC, ix, n_lines, d_vl.as<mga_gaf_vline_t>(), 0, 0, d_lc.as<mg_llchain_t>(), d_a.as<mg128_t>(), flag, d_len.as<int32_t>(), d_hdr.as<int32_t>(), d_hb.as<int32_t>(), off, dst);
+	};
+	int32_t hb[2];
+	int64_t tot = 0;
+	if (lines(0, 0) < 0 || mga_dev_scan_i32_to_i64(SC, d_len.as<int32_t>(), n_lines, d_off.as<int64_t>()) < 0 || mga_ssync(SC) < 0 || mga_d2h(hb, d_hb.p, 8) < 0 ||
+		mga_d2h(&tot, d_off.as<int64_t>() + n_lines, 8) < 0) return -1;
+	if (hb[0] || hb[1]) { // as a chunk does: counted, then the host writer
+		mga_gaf_vert_count(0, hb[0] != 0, hb[0] == 0);
+		*out_len = mga_gaf_vert_host(gi->g, n_reads, qnames, qname_off, qlens, gc_off, ch, lc, a, pool, flag, out);
+		return 0;
+	}
+	char *h = (char*)malloc((size_t)tot + 1);
+	if (h == 0 || !d_out.alloc((size_t)tot + 64)) { free(h); mga_set_error("gaf_vert_batch: out of memory"); return -1; }
+	if (mga_dmemset_s(SC, d_out.p, 0, (size_t)tot + 64) < 0 || lines(d_off.as<int64_t>(), d_out.as<char>()) < 0 || mga_ssync(SC) < 0 || (tot > 0 && mga_d2h(h, d_out.p, (size_t)tot) < 0)) { free(h); return -1; }
+	mga_gaf_vert_count(n_vlines, 0, 0);
+	h[tot] = 0;
+	*out = h, *out_len = tot;
+	return 0;
+}
+
 extern "C" int mga_sort128x_batch(int n, mg128_t *a, const int64_t *a_off)
 {
 	if (mga_dev_init() < 0) return -1;
