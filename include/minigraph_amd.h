@@ -522,6 +522,11 @@ int mga_wfa_seg_batch(int n, const char *tseq, const int64_t *t_off, const char 
 int64_t mga_wfa_seg_bytes(int32_t tl, int32_t ql, int32_t step);
 int32_t mga_wfa_seg_step(int32_t tl, int32_t ql);
 void mga_wfa_seg_stats(int64_t *problems, int64_t *snapshots, int reset);
+/* MGA_WFA_SEG_GRID (default 1; 0: off): the first pass of the problems with W >= MGA_WFA_SEG_GRID_MIN (default 16384) runs grid-wide, the band cut into tiles of
+ * MGA_WFA_SEG_GRID_TILE diagonals (default 1024), a workgroup each, advanced MGA_WFA_SEG_GRID_BLOCK scores (default 64, at most the tile and 256) per launch; results
+ * are the same.  Workspace: the formula above plus 1360 BLOCK max(1, floor(W / TILE)) bytes of halo staging.  mga_wfa_seg_grid_stats: problems that took this
+ * form, kernels launched for them and the most tiles one problem was cut into, since the last reset; mga_wfa_seg_stats counts both forms. */
+void mga_wfa_seg_grid_stats(int64_t *problems, int64_t *launches, int64_t *max_tiles, int reset);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,8 @@ def load():
     L.mga_wfa_seg_step.restype = C.c_int32
     L.mga_wfa_seg_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
     L.mga_wfa_seg_stats.restype = None
+    L.mga_wfa_seg_grid_stats.argtypes = [C.POINTER(C.c_int64)] * 3 + [C.c_int]
+    L.mga_wfa_seg_grid_stats.restype = None
     L.gfa_read.argtypes = [C.c_char_p]
     L.gfa_read.restype = C.c_void_p
     L.gfa_destroy.argtypes = [C.c_void_p]
@@ -181,6 +183,14 @@ def wfa_seg_stats(reset=False):
     p, s = C.c_int64(0), C.c_int64(0)
     load().mga_wfa_seg_stats(C.byref(p), C.byref(s), 1 if reset else 0)
     return {"problems": p.value, "snapshots": s.value}
+
+
+def wfa_seg_grid_stats(reset=False):
+    """the grid-wide form of the rung's first pass (MGA_WFA_SEG_GRID=1): problems that took it, kernels launched for them and the most tiles
+    one problem was cut into, since the last reset"""
+    p, n, t = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    load().mga_wfa_seg_grid_stats(C.byref(p), C.byref(n), C.byref(t), 1 if reset else 0)
+    return {"problems": p.value, "launches": n.value, "max_tiles": t.value}
 
 
 def wfa_seg_bytes(tl, ql, step=0):

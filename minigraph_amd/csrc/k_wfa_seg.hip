@@ -8,6 +8,7 @@
 // The CIGAR equals the full mode's for every step (tests/test_wfa_seg.py pins that to the unmodified reference), so the step is the
 // device's to choose: the host takes the one that needs the least memory (wseg_plan below; formula in DESIGN.md 4).
 //
+// Two forms of pass 1: the one of this file, and for wide problems the grid-wide one of wfa_seg_grid.h (tiles of diagonals; MGA_WFA_SEG_GRID); the rest is shared.
 // One WORKGROUP (up to 1024 threads) per problem, threads strided over the diagonals of a slice.  What k_wfa.hip states about the
 // recurrence, NEG_INF outside a slice, band growth, the 256-score trim and the extension on raw bytes holds here verbatim.
 //
@@ -296,26 +297,17 @@ __device__ wseg_fwd_t wseg_forward(wseg_lds_t &S, const wseg_ws_t &W, const wseg
 	return R;
 }
 
-__global__ void __launch_bounds__(1024) k_wfa_seg(const wseg_job_t *__restrict__ jobs, const mga_wfa_prob_t *__restrict__ prob, const char *__restrict__ tseq, const char *__restrict__ qseq,
-												  mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out, uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used,
-												  char *__restrict__ ws_base, wseg_pen_t P)
+// What follows pass 1, for one problem on one workgroup: the walk over the chain of snapshots, pass 2, the traceback and the result.  status / n_seg / last: how pass 1 ended.
+__device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, const wseg_job_t &J, const wseg_ws_t &W, const wseg_pen_t &P, const char *ts, const char *qs,
+											int32_t status, int32_t n_seg, int32_t last1, mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out,
+											uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used)
 {
-	__shared__ wseg_lds_t S;
-	__shared__ int32_t walk_s;
 	const int tid = threadIdx.x;
-	const wseg_job_t J = jobs[blockIdx.x];
-	const wseg_ws_t W = wseg_carve(ws_base + J.ws_off, J);
-	const mga_wfa_prob_t pb = prob[J.pi];
-	const char *ts = tseq + pb.t_off, *qs = qseq + pb.q_off;
 	const int32_t oe1 = P.o1 + P.e1, oe2 = P.o2 + P.e2;
-	int32_t status = WSEG_OK, n_seg = 0;
-
-	if (J.max_snap > 0) { // ---- pass 1 (a problem whose score bound lies below the step takes no snapshot: nothing to learn from it)
-		const wseg_fwd_t F = wseg_forward<1>(S, W, J, P, ts, qs, 0);
-		status = F.status, n_seg = F.n_snap;
+	if (J.max_snap > 0) {
 		__syncthreads(); // the snapshots of every wave are visible to the walk
 		if (tid == 0) { // wf_traceback_seg (miniwfa.c:528-549): one dependent read per snapshot
-			int32_t last = F.last, bad = 0;
+			int32_t last = last1, bad = 0;
 			for (int32_t j = n_seg - 1; status == WSEG_OK && j >= 0; --j) {
 				const wseg_snap_t *M = &W.meta[j];
 				if (last < 0 || last >= M->n) { bad = 1; break; }
@@ -407,9 +399,29 @@ __global__ void __launch_bounds__(1024) k_wfa_seg(const wseg_job_t *__restrict__
 		res[J.pi] = r;
 		wseg_out_t o;
 		o.score = r.score, o.n_snap = n_seg, o.status = status, o.pad = 0, o.n_iter = n_iter;
-		out[blockIdx.x] = o;
+		*out = o;
 	}
 }
+
+__global__ void __launch_bounds__(1024) k_wfa_seg(const wseg_job_t *__restrict__ jobs, const mga_wfa_prob_t *__restrict__ prob, const char *__restrict__ tseq, const char *__restrict__ qseq,
+												  mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out, uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used,
+												  char *__restrict__ ws_base, wseg_pen_t P)
+{
+	__shared__ wseg_lds_t S;
+	__shared__ int32_t walk_s;
+	const wseg_job_t J = jobs[blockIdx.x];
+	const wseg_ws_t W = wseg_carve(ws_base + J.ws_off, J);
+	const mga_wfa_prob_t pb = prob[J.pi];
+	const char *ts = tseq + pb.t_off, *qs = qseq + pb.q_off;
+	int32_t status = WSEG_OK, n_seg = 0, last = 0;
+	if (J.max_snap > 0) { // ---- pass 1 (a problem whose score bound lies below the step takes no snapshot: nothing to learn from it)
+		const wseg_fwd_t F = wseg_forward<1>(S, W, J, P, ts, qs, 0);
+		status = F.status, n_seg = F.n_snap, last = F.last;
+	}
+	wseg_finish(S, walk_s, J, W, P, ts, qs, status, n_seg, last, res, out + blockIdx.x, pool, pool_cap, pool_used);
+}
+
+#include "wfa_seg_grid.h" // the grid-wide form of pass 1 (MGA_WFA_SEG_GRID=1): k_wseg_grid_init / _stage / _block / _p2
 
 // ---- host: sizes -------------------------------------------------------------------------------
 // W = tl + ql + 1 diagonals exist; at score s the band holds at most B(s) = min(W, 2 s + 1) of them.
@@ -510,10 +522,31 @@ extern "C" double mga_wfa_seg_seconds(void) { return 1e-9 * (double)__atomic_loa
 extern "C" int64_t mga_wfa_seg_cells(void) { return __atomic_load_n(&g_seg_cells, __ATOMIC_RELAXED); }
 extern "C" int32_t mga_wfa_seg_last_step(void) { return (int32_t)__atomic_load_n(&g_seg_last_step, __ATOMIC_RELAXED); }
 
+// the grid-wide form: problems it ran, kernels it launched for them, and the most tiles one problem was cut into (as the device derived them), since the last reset
+static long long g_segg_problems, g_segg_launches, g_segg_max_tiles;
+extern "C" void mga_wfa_seg_grid_stats(int64_t *problems, int64_t *launches, int64_t *max_tiles, int reset)
+{
+	if (problems) *problems = __atomic_load_n(&g_segg_problems, __ATOMIC_RELAXED);
+	if (launches) *launches = __atomic_load_n(&g_segg_launches, __ATOMIC_RELAXED);
+	if (max_tiles) *max_tiles = __atomic_load_n(&g_segg_max_tiles, __ATOMIC_RELAXED);
+	if (reset) { __atomic_store_n(&g_segg_problems, 0, __ATOMIC_RELAXED); __atomic_store_n(&g_segg_launches, 0, __ATOMIC_RELAXED); __atomic_store_n(&g_segg_max_tiles, 0, __ATOMIC_RELAXED); }
+}
+
+// MGA_WFA_SEG_GRID_TILE diagonals per tile, MGA_WFA_SEG_GRID_BLOCK scores per launch (at most a tile's width: the halo argument of wfa_seg_grid.h, and at most 256: the trim)
+struct wseg_grid_par_t { int32_t tile, block; };
+
+static long long wseg_env(const char *name, long long dflt, long long lo, long long hi)
+{
+	const char *e = getenv(name);
+	long long v = e && *e ? atoll(e) : dflt;
+	return v < lo ? lo : v > hi ? hi : v;
+}
+
 // ---- host: driver ------------------------------------------------------------------------------
 // Runs the n problems ids[] (NULL: 0 .. n-1) of d_prob, whose lengths the caller read back into h_tl / h_ql (indexed like ids), as many side by side as fit
 // MGA_WFA_SEG_BUDGET bytes of workspace (default 32 GiB; a single problem may take more, up to what the device has free).  Results in d_res / the pool.
-extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step)
+// gp: the grid-wide form of pass 1 with these parameters; NULL: the workgroup form.
+static int wseg_run(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step, const wseg_grid_par_t *gp)
 {
 	if (n <= 0) return 0;
 	const double t0 = mga_wtime();
@@ -528,9 +561,16 @@ extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, c
 		memset(&J, 0, sizeof(J));
 		J.pi = ids ? ids[i] : i, J.tl = h_tl[i], J.ql = h_ql[i], J.step = wseg_step_for(J.tl, J.ql, step);
 		if (wseg_plan(J) < 0) { mga_set_error("WFA low-memory rung: a problem of %d x %d bases is beyond its 32-bit indices", J.tl, J.ql); return -1; }
+		if (gp) J.wmax = J.tl + J.ql + 1; // rings indexed by the diagonal itself (in fact no change: 2 smax + 1 >= W for every tl, ql)
 		bytes[i] = wseg_parts(J).total;
+		if (gp) { // + the tiles' staging areas
+			const int64_t ntile = J.wmax / gp->tile > 1 ? J.wmax / gp->tile : 1;
+			bytes[i] += (ntile * wseg_gstage_len(gp->block) * 4 + 255) & ~(int64_t)255;
+		}
 	}
 	std::vector<wseg_out_t> out;
+	std::vector<wseg_gjob_t> gjob;
+	std::vector<wseg_gres_t> gres;
 	for (int i0 = 0; i0 < n;) {
 		int i1 = i0;
 		int64_t tot = 0;
@@ -545,18 +585,75 @@ extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, c
 						  nb, job[i0].tl, job[i0].ql, job[i0].step, (long long)tot, (long long)fr);
 			return -1;
 		}
-		if (mga_dbuf_reserve(&sc->wfa_seg_job, (size_t)nb * (sizeof(wseg_job_t) + sizeof(wseg_out_t))) < 0) return -1;
-		wseg_job_t *d_job = (wseg_job_t*)sc->wfa_seg_job.p;
-		wseg_out_t *d_out = (wseg_out_t*)(d_job + nb);
-		if (mga_h2d(d_job, job.data() + i0, (size_t)nb * sizeof(wseg_job_t)) < 0) return -1;
 		int nt = (wtop + 63) / 64 * 64;
 		nt = nt < 64 ? 64 : nt > 1024 ? 1024 : nt;
 		const int kid = MGA_K_WFA0 + 8; // accounted with the widest HBM tier, like the unbounded one (k_wfa.hip)
-		mga_prof_begin(st, kid);
-		hipLaunchKernelGGL(k_wfa_seg, dim3(nb), dim3(nt), 0, st, (const wseg_job_t*)d_job, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool, (long long)jb->pool_cap, jb->d_pool_used,
-						   (char*)sc->wfa_seg_ws.p, g_pen);
-		mga_prof_end(st, kid);
-		MGA_HIP_CHECK(hipGetLastError());
+		wseg_out_t *d_out;
+		if (!gp) {
+			if (mga_dbuf_reserve(&sc->wfa_seg_job, (size_t)nb * (sizeof(wseg_job_t) + sizeof(wseg_out_t))) < 0) return -1;
+			wseg_job_t *d_job = (wseg_job_t*)sc->wfa_seg_job.p;
+			d_out = (wseg_out_t*)(d_job + nb);
+			if (mga_h2d(d_job, job.data() + i0, (size_t)nb * sizeof(wseg_job_t)) < 0) return -1;
+			mga_prof_begin(st, kid);
+			hipLaunchKernelGGL(k_wfa_seg, dim3(nb), dim3(nt), 0, st, (const wseg_job_t*)d_job, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool, (long long)jb->pool_cap, jb->d_pool_used,
+							   (char*)sc->wfa_seg_ws.p, g_pen);
+			mga_prof_end(st, kid);
+			MGA_HIP_CHECK(hipGetLastError());
+		} else { // ---- the grid-wide form: init | stage, block | stage, block | ... | pass 2, all on this stream; the kernel boundary is the only grid-wide synchronisation
+			if (mga_dbuf_reserve(&sc->wfa_seg_job, (size_t)nb * (sizeof(wseg_gjob_t) + 2 * sizeof(wseg_gstate_t) + sizeof(wseg_out_t) + sizeof(wseg_gres_t))) < 0) return -1;
+			wseg_gjob_t *d_gjob = (wseg_gjob_t*)sc->wfa_seg_job.p;
+			wseg_gstate_t *d_state = (wseg_gstate_t*)(d_gjob + nb);
+			d_out = (wseg_out_t*)(d_state + 2 * nb);
+			wseg_gres_t *d_gres = (wseg_gres_t*)(d_out + nb);
+			gjob.resize((size_t)nb), gres.resize((size_t)nb);
+			int32_t s_top = 0;
+			for (int i = 0; i < nb; ++i) {
+				wseg_gjob_t &g = gjob[i];
+				g.J = job[i0 + i], g.tile = gp->tile, g.block = gp->block;
+				g.stage_off = g.J.ws_off + wseg_parts(g.J).total;
+				if (g.J.smax > s_top) s_top = g.J.smax;
+			}
+			if (mga_h2d(d_gjob, gjob.data(), (size_t)nb * sizeof(wseg_gjob_t)) < 0) return -1;
+			int ntg = (gp->tile + 63) / 64 * 64;
+			ntg = ntg > 1024 ? 1024 : ntg;
+			char *ws = (char*)sc->wfa_seg_ws.p;
+			long long launches = 2;
+			const double tg0 = mga_wtime();
+			mga_prof_begin(st, kid);
+			hipLaunchKernelGGL(k_wseg_grid_init, dim3(nb), dim3(64), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, d_gres, ws);
+			// Block k starts at a score <= k block, where the band holds at most min(W, 2 k block + 1) diagonals: the host sizes the grid by that bound, the device derives
+			// the tiles from the band as it is, and a workgroup past the last tile returns at once.  The host looks at the `done` flags every 32 blocks only; the
+			// launches enqueued behind a problem's end return on the flag.  (Every block advances an unfinished problem by a score at least: s_top + 1 blocks end them all.)
+			for (int32_t k = 0; k <= s_top; ++k) {
+				const int64_t wb = 2LL * k * gp->block + 1 < wtop ? 2LL * k * gp->block + 1 : wtop;
+				const int gx = (int)(wb / gp->tile > 1 ? wb / gp->tile : 1);
+				hipLaunchKernelGGL(k_wseg_grid_stage, dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, d_state, d_gres, ws, k & 1);
+				hipLaunchKernelGGL(k_wseg_grid_block, dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, d_gres, ws, g_pen, k & 1);
+				launches += 2;
+				if ((k & 31) == 31) {
+					MGA_HIP_CHECK(hipGetLastError());
+					if (mga_ssync(sc) < 0 || mga_d2h(gres.data(), d_gres, (size_t)nb * sizeof(wseg_gres_t)) < 0) return -1;
+					int live = 0;
+					for (int i = 0; i < nb; ++i) live += !gres[i].done;
+					if (!live) break;
+				}
+			}
+			const bool trace = wseg_env("MGA_WFA_SEG_GRID_TRACE", 0, 0, 1) != 0; // one line per launch batch on stderr, the two passes timed apart (one more sync)
+			if (trace && mga_ssync(sc) < 0) return -1;
+			const double t2 = mga_wtime();
+			hipLaunchKernelGGL(k_wseg_grid_p2, dim3(nb), dim3(nt), 0, st,(const wseg_gjob_t*)d_gjob, (const wseg_gres_t*)d_gres, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool,
+							   (long long)jb->pool_cap, jb->d_pool_used, ws, g_pen);
+			mga_prof_end(st, kid);
+			MGA_HIP_CHECK(hipGetLastError());
+			if (mga_ssync(sc) < 0 || mga_d2h(gres.data(), d_gres, (size_t)nb * sizeof(wseg_gres_t)) < 0) return -1;
+			long long mt = 0;
+			for (int i = 0; i < nb; ++i) if (gres[i].max_tiles > mt) mt = gres[i].max_tiles;
+			if (trace) fprintf(stderr, "wfa_seg_grid: %d problem(s), tile %d, block %d: pass 1 %.3f s (from the first launch) in %lld launches, pass 2 %.3f s, at most %lld tiles, %lld bytes of workspace\n",
+							   nb, gp->tile, gp->block, t2 - tg0, launches, mga_wtime() - t2, mt, (long long)tot);
+			if (mt > __atomic_load_n(&g_segg_max_tiles, __ATOMIC_RELAXED)) __atomic_store_n(&g_segg_max_tiles, mt, __ATOMIC_RELAXED);
+			__atomic_fetch_add(&g_segg_problems, (long long)nb, __ATOMIC_RELAXED);
+			__atomic_fetch_add(&g_segg_launches, launches, __ATOMIC_RELAXED);
+		}
 		out.resize((size_t)nb);
 		if (mga_ssync(sc) < 0 || mga_d2h(out.data(), d_out, (size_t)nb * sizeof(wseg_out_t)) < 0) return -1;
 		for (int i = 0; i < nb; ++i) {
@@ -576,4 +673,24 @@ extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, c
 	}
 	__atomic_fetch_add(&g_seg_ns, (long long)((mga_wtime() - t0) * 1e9), __ATOMIC_RELAXED);
 	return 0;
+}
+
+// MGA_WFA_SEG_GRID (default 1 since the measurement of DESIGN 4: 8.2 s against 128.9 s; 0: the workgroup form for everything): the problems of at least
+// MGA_WFA_SEG_GRID_MIN diagonals (W = tl + ql + 1) take the grid-wide form, the others the workgroup form.  The default of 16384 for that is set by argument, not
+// by measurement: below it the workgroup form makes at most 16 trips of its 1024 threads per score, and the grid form pays two launches per block and cuts such
+// a band into fewer tiles than a sixteenth of the CUs could take.
+extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_t *ids, const int32_t *h_tl, const int32_t *h_ql, int32_t step)
+{
+	if (!wseg_env("MGA_WFA_SEG_GRID", 1, 0, 1)) return wseg_run(sc, jb, n, ids, h_tl, h_ql, step, 0);
+	wseg_grid_par_t gp;
+	gp.tile = (int32_t)wseg_env("MGA_WFA_SEG_GRID_TILE", 1024, 16, 1 << 20);
+	gp.block = (int32_t)wseg_env("MGA_WFA_SEG_GRID_BLOCK", 64, 1, gp.tile < 256 ? gp.tile : 256);
+	const long long wmin = wseg_env("MGA_WFA_SEG_GRID_MIN", 16384, 0, 1LL << 40);
+	std::vector<int32_t> id[2], tl[2], ql[2];
+	for (int i = 0; i < n; ++i) {
+		const int g = (long long)h_tl[i] + h_ql[i] + 1 >= wmin;
+		id[g].push_back(ids ? ids[i] : i), tl[g].push_back(h_tl[i]), ql[g].push_back(h_ql[i]);
+	}
+	if (wseg_run(sc, jb, (int)id[0].size(), id[0].data(), tl[0].data(), ql[0].data(), step, 0) < 0) return -1;
+	return wseg_run(sc, jb, (int)id[1].size(), id[1].data(), tl[1].data(), ql[1].data(), step, &gp);
 }

@@ -13,7 +13,7 @@ reference's mwf_wfa_auto().  --rung-only: the same pair through the rung alone (
 the same cells first.  Prints the wall time of the rung, the chosen step, the snapshot count and wfa_seg_bytes.  Needs oracle/_ref/libmgref.so, or
 --ref-cache with an earlier result of it for the same pair.
 
-    python minigraph_amd/tools/wfa_seg_check.py [--len 150000] [--plan-only] [--rung-only] [--ref-cache FILE.npz]
+    python minigraph_amd/tools/wfa_seg_check.py [--len 150000] [--plan-only] [--rung-only] [--ref-cache FILE.npz] [--grid TILE,BLOCK | --grid 0]
 """
 import argparse
 import ctypes as C
@@ -92,7 +92,14 @@ def main():
     ap.add_argument("--rung-only", action="store_true", help="run the pair through the low-memory rung alone (mga.wfa_seg_batch) instead of the whole ladder")
     ap.add_argument("--ref-only", action="store_true", help="compute the reference's result into --ref-cache on the CPU, run nothing on the GPU")
     ap.add_argument("--ref-cache", default=None, help="npz file with the reference's result for this pair: read when it matches the pair, written otherwise")
+    ap.add_argument("--grid", default=None, metavar="TILE,BLOCK", help="the grid-wide form of the rung's first pass (MGA_WFA_SEG_GRID=1) with this tile and block; "
+                    "the library then reports the two passes apart on stderr.  0: the workgroup form (MGA_WFA_SEG_GRID=0).  Not given: the library's defaults")
     a = ap.parse_args()
+    if a.grid == "0":
+        os.environ["MGA_WFA_SEG_GRID"] = "0"
+    elif a.grid:
+        tile, block = a.grid.split(",")
+        os.environ.update(MGA_WFA_SEG_GRID="1", MGA_WFA_SEG_GRID_TILE=tile, MGA_WFA_SEG_GRID_BLOCK=block, MGA_WFA_SEG_GRID_TRACE="1")
     ts, qs = build_pair(a.len, a.seed)
     subs = plan_of(ts, qs)
     step, nbytes = mga.wfa_seg_step(len(ts), len(qs)), mga.wfa_seg_bytes(len(ts), len(qs), 0)
@@ -131,6 +138,8 @@ def main():
     st = mga.wfa_seg_stats()
     print("device %s: score %d, %d operators, %.1f s in all; low-memory rung: %d problem(s), %.1f s, step %d, %d snapshots"
           % ("wfa_seg_batch" if a.rung_only else "wfa_batch", sc[0], len(cg[0]), wall, st["problems"], L.mga_wfa_seg_seconds(), L.mga_wfa_seg_last_step(), st["snapshots"]))
+    if a.grid != "0":
+        print("grid-wide first pass (tile,block %s): %s" % (a.grid or "by default",mga.wfa_seg_grid_stats()))
     cells = L.mga_wfa_seg_cells()
     print("traceback the rung's second pass wrote (one byte per cell of its narrowed band): %d = %.2f GiB" % (cells, cells / 2.0**30))
     if st["problems"] != 1:
