@@ -527,6 +527,10 @@ void mga_wfa_seg_stats(int64_t *problems, int64_t *snapshots, int reset);
  * are the same.  Workspace: the formula above plus 1360 BLOCK max(1, floor(W / TILE)) bytes of halo staging.  mga_wfa_seg_grid_stats: problems that took this
  * form, kernels launched for them and the most tiles one problem was cut into, since the last reset; mga_wfa_seg_stats counts both forms. */
 void mga_wfa_seg_grid_stats(int64_t *problems, int64_t *launches, int64_t *max_tiles, int reset);
+/* MGA_WFA_SEG_GRID_P2 (default 1; 0: the second pass on one workgroup per problem): the second pass of the problems that took the grid-wide first pass runs over the same tiles and blocks (the same TILE / BLOCK),
+ * re-tiled from one tile after every checkpoint; results are the same, the workspace too (its halos take half of the first pass's staging).  mga_wfa_seg_grid_p2_stats:
+ * problems whose second pass took this form, kernels launched for it and the most tiles of one problem, since the last reset; mga_wfa_seg_grid_stats counts the first pass only. */
+void mga_wfa_seg_grid_p2_stats(int64_t *problems, int64_t *launches, int64_t *max_tiles, int reset);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,8 @@ def load():
     L.mga_wfa_seg_stats.restype = None
     L.mga_wfa_seg_grid_stats.argtypes = [C.POINTER(C.c_int64)] * 3 + [C.c_int]
     L.mga_wfa_seg_grid_stats.restype = None
+    L.mga_wfa_seg_grid_p2_stats.argtypes = [C.POINTER(C.c_int64)] * 3 + [C.c_int]
+    L.mga_wfa_seg_grid_p2_stats.restype = None
     L.gfa_read.argtypes = [C.c_char_p]
     L.gfa_read.restype = C.c_void_p
     L.gfa_destroy.argtypes = [C.c_void_p]
@@ -190,6 +192,14 @@ def wfa_seg_grid_stats(reset=False):
     one problem was cut into, since the last reset"""
     p, n, t = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     load().mga_wfa_seg_grid_stats(C.byref(p), C.byref(n), C.byref(t), 1 if reset else 0)
+    return {"problems": p.value, "launches": n.value, "max_tiles": t.value}
+
+
+def wfa_seg_grid_p2_stats(reset=False):
+    """the grid-wide form of the rung's second pass (MGA_WFA_SEG_GRID_P2=1): problems whose second pass took it, kernels launched for it and the
+    most tiles of one problem, since the last reset"""
+    p, n, t = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    load().mga_wfa_seg_grid_p2_stats(C.byref(p), C.byref(n), C.byref(t), 1 if reset else 0)
     return {"problems": p.value, "launches": n.value, "max_tiles": t.value}
 
 

@@ -8,7 +8,8 @@
 // The CIGAR equals the full mode's for every step (tests/test_wfa_seg.py pins that to the unmodified reference), so the step is the
 // device's to choose: the host takes the one that needs the least memory (wseg_plan below; formula in DESIGN.md 4).
 //
-// Two forms of pass 1: the one of this file, and for wide problems the grid-wide one of wfa_seg_grid.h (tiles of diagonals; MGA_WFA_SEG_GRID); the rest is shared.
+// Two forms of pass 1: the one of this file, and for wide problems the grid-wide one of wfa_seg_grid.h (tiles of diagonals; MGA_WFA_SEG_GRID); the rest is shared,
+// unless MGA_WFA_SEG_GRID_P2=1 sends pass 2 of those problems over the same tiles (then the snapshot walk and the tail of this file run in kernels of their own).
 // One WORKGROUP (up to 1024 threads) per problem, threads strided over the diagonals of a slice.  What k_wfa.hip states about the
 // recurrence, NEG_INF outside a slice, band growth, the 256-score trim and the extension on raw bytes holds here verbatim.
 //
@@ -297,13 +298,11 @@ __device__ wseg_fwd_t wseg_forward(wseg_lds_t &S, const wseg_ws_t &W, const wseg
 	return R;
 }
 
-// What follows pass 1, for one problem on one workgroup: the walk over the chain of snapshots, pass 2, the traceback and the result.  status / n_seg / last: how pass 1 ended.
-__device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, const wseg_job_t &J, const wseg_ws_t &W, const wseg_pen_t &P, const char *ts, const char *qs,
-											int32_t status, int32_t n_seg, int32_t last1, mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out,
-											uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used)
+// What follows pass 1, for one problem on one workgroup, in three parts: the walk over the chain of snapshots (wseg_walk), pass 2, and the tail (wseg_tail: the traceback
+// and the result).  wseg_finish runs them in turn; the grid-wide second pass of wfa_seg_grid.h calls the walk and the tail on their own.  status / n_seg / last1: how pass 1 ended.
+__device__ __forceinline__ int32_t wseg_walk(int32_t &walk_s, const wseg_job_t &J, const wseg_ws_t &W, int32_t status, int32_t n_seg, int32_t last1)
 {
 	const int tid = threadIdx.x;
-	const int32_t oe1 = P.o1 + P.e1, oe2 = P.o2 + P.e2;
 	if (J.max_snap > 0) {
 		__syncthreads(); // the snapshots of every wave are visible to the walk
 		if (tid == 0) { // wf_traceback_seg (miniwfa.c:528-549): one dependent read per snapshot
@@ -322,16 +321,23 @@ __device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, cons
 		__syncthreads();
 		if (status == WSEG_OK && walk_s) status = WSEG_E_WALK;
 	}
+	return status;
+}
 
-	int32_t score = -1, n_cig = 0;
-	int64_t n_iter = 0, cig_off = 0;
-	if (status == WSEG_OK) { // ---- pass 2
-		const wseg_fwd_t F = wseg_forward<2>(S, W, J, P, ts, qs, n_seg);
-		status = F.status, n_iter = F.n_iter, score = F.s;
+// status / score / last / n_iter: how pass 2 ended (status may be an error from before it: then the result record alone is written)
+__device__ __forceinline__ void wseg_tail(wseg_lds_t &S, const wseg_job_t &J, const wseg_ws_t &W, const wseg_pen_t &P, const char *ts, const char *qs, int32_t status, int32_t score,
+										  int32_t last2, int64_t n_iter, int32_t n_seg, mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out, uint32_t *__restrict__ pool,
+										  long long pool_cap, unsigned long long *pool_used)
+{
+	const int tid = threadIdx.x;
+	const int32_t oe1 = P.o1 + P.e1, oe2 = P.o2 + P.e2;
+	int32_t n_cig = 0;
+	int64_t cig_off = 0;
+	{
 		__syncthreads(); // the traceback rows of every wave are visible to the walk
 		if (status == WSEG_OK && tid < 64) { // ---- traceback (miniwfa.c:329-377) by the first wave: match runs by ballot, state walk uniform
 			const int lane = tid;
-			int32_t i = J.ql - 1, k = J.tl - 1, sc = F.s, last = F.last;
+			int32_t i = J.ql - 1, k = J.tl - 1, sc = score, last = last2;
 			int32_t cur_op = -1, cur_len = 0;
 			bool overflow = false;
 #define PUSH(op, len) do { \
@@ -354,7 +360,7 @@ __device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, cons
 					if (tot > 0) PUSH(7, tot);
 					if (i < 0 || k < 0) break;
 				}
-				if (sc < 0 || sc > F.s) { overflow = true; n_cig = -1; break; } // (cannot happen: the walk stays inside the rows pass 2 wrote; never read outside the workspace)
+				if (sc < 0 || sc > score) { overflow = true; n_cig = -1; break; } // (cannot happen: the walk stays inside the rows pass 2 wrote; never read outside the workspace)
 				const int64_t at_tb = W.row[sc] + ((i - k) - W.rlo[sc]);
 				if (at_tb < W.row[sc] || at_tb >= J.tbcap) { overflow = true; n_cig = -1; break; }
 				const uint32_t x = W.tb[at_tb];
@@ -403,6 +409,20 @@ __device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, cons
 	}
 }
 
+__device__ __forceinline__ void wseg_finish(wseg_lds_t &S, int32_t &walk_s, const wseg_job_t &J, const wseg_ws_t &W, const wseg_pen_t &P, const char *ts, const char *qs,
+											int32_t status, int32_t n_seg, int32_t last1, mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out,
+											uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used)
+{
+	status = wseg_walk(walk_s, J, W, status, n_seg, last1);
+	int32_t score = -1, last = 0;
+	int64_t n_iter = 0;
+	if (status == WSEG_OK) { // ---- pass 2
+		const wseg_fwd_t F = wseg_forward<2>(S, W, J, P, ts, qs, n_seg);
+		status = F.status, n_iter = F.n_iter, score = F.s, last = F.last;
+	}
+	wseg_tail(S, J, W, P, ts, qs, status, score, last, n_iter, n_seg, res, out, pool, pool_cap, pool_used);
+}
+
 __global__ void __launch_bounds__(1024) k_wfa_seg(const wseg_job_t *__restrict__ jobs, const mga_wfa_prob_t *__restrict__ prob, const char *__restrict__ tseq, const char *__restrict__ qseq,
 												  mga_wfa_res_t *__restrict__ res, wseg_out_t *__restrict__ out, uint32_t *__restrict__ pool, long long pool_cap, unsigned long long *pool_used,
 												  char *__restrict__ ws_base, wseg_pen_t P)
@@ -421,7 +441,7 @@ __global__ void __launch_bounds__(1024) k_wfa_seg(const wseg_job_t *__restrict__
 	wseg_finish(S, walk_s, J, W, P, ts, qs, status, n_seg, last, res, out + blockIdx.x, pool, pool_cap, pool_used);
 }
 
-#include "wfa_seg_grid.h" // the grid-wide form of pass 1 (MGA_WFA_SEG_GRID=1): k_wseg_grid_init / _stage / _block / _p2
+#include "wfa_seg_grid.h" // the grid-wide form (MGA_WFA_SEG_GRID=1): k_wseg_grid_init / _stage<1> / _block<1> / _p2, or, for pass 2 (MGA_WFA_SEG_GRID_P2=1), _init2 / _stage<2> / _block<2> / _tail
 
 // ---- host: sizes -------------------------------------------------------------------------------
 // W = tl + ql + 1 diagonals exist; at score s the band holds at most B(s) = min(W, 2 s + 1) of them.
@@ -533,7 +553,17 @@ extern "C" void mga_wfa_seg_grid_stats(int64_t *problems, int64_t *launches, int
 }
 
 // MGA_WFA_SEG_GRID_TILE diagonals per tile, MGA_WFA_SEG_GRID_BLOCK scores per launch (at most a tile's width: the halo argument of wfa_seg_grid.h, and at most 256: the trim)
-struct wseg_grid_par_t { int32_t tile, block; };
+// the grid-wide form of pass 2 (MGA_WFA_SEG_GRID_P2=1): the same three figures for its own launches (init, stage / block, tail) and tiles
+static long long g_segg2_problems, g_segg2_launches, g_segg2_max_tiles;
+extern "C" void mga_wfa_seg_grid_p2_stats(int64_t *problems, int64_t *launches, int64_t *max_tiles, int reset)
+{
+	if (problems) *problems = __atomic_load_n(&g_segg2_problems, __ATOMIC_RELAXED);
+	if (launches) *launches = __atomic_load_n(&g_segg2_launches, __ATOMIC_RELAXED);
+	if (max_tiles) *max_tiles = __atomic_load_n(&g_segg2_max_tiles, __ATOMIC_RELAXED);
+	if (reset) { __atomic_store_n(&g_segg2_problems, 0, __ATOMIC_RELAXED); __atomic_store_n(&g_segg2_launches, 0, __ATOMIC_RELAXED); __atomic_store_n(&g_segg2_max_tiles, 0, __ATOMIC_RELAXED); }
+}
+
+struct wseg_grid_par_t { int32_t tile, block, p2; }; // p2: pass 2 grid-wide as well (MGA_WFA_SEG_GRID_P2)
 
 static long long wseg_env(const char *name, long long dflt, long long lo, long long hi)
 {
@@ -600,7 +630,7 @@ static int wseg_run(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_
 			mga_prof_end(st, kid);
 			MGA_HIP_CHECK(hipGetLastError());
 		} else { // ---- the grid-wide form: init | stage, block | stage, block | ... | pass 2, all on this stream; the kernel boundary is the only grid-wide synchronisation
-			if (mga_dbuf_reserve(&sc->wfa_seg_job, (size_t)nb * (sizeof(wseg_gjob_t) + 2 * sizeof(wseg_gstate_t) + sizeof(wseg_out_t) + sizeof(wseg_gres_t))) < 0) return -1;
+			if (mga_dbuf_reserve(&sc->wfa_seg_job, (size_t)nb * (sizeof(wseg_gjob_t) + 2 * sizeof(wseg_gstate_t) + sizeof(wseg_out_t) + 2 * sizeof(wseg_gres_t))) < 0) return -1; // (the outcome of pass 1, then of a grid-wide pass 2)
 			wseg_gjob_t *d_gjob = (wseg_gjob_t*)sc->wfa_seg_job.p;
 			wseg_gstate_t *d_state = (wseg_gstate_t*)(d_gjob + nb);
 			d_out = (wseg_out_t*)(d_state + 2 * nb);
@@ -627,8 +657,8 @@ static int wseg_run(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_
 			for (int32_t k = 0; k <= s_top; ++k) {
 				const int64_t wb = 2LL * k * gp->block + 1 < wtop ? 2LL * k * gp->block + 1 : wtop;
 				const int gx = (int)(wb / gp->tile > 1 ? wb / gp->tile : 1);
-				hipLaunchKernelGGL(k_wseg_grid_stage, dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, d_state, d_gres, ws, k & 1);
-				hipLaunchKernelGGL(k_wseg_grid_block, dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, d_gres, ws, g_pen, k & 1);
+				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wseg_grid_stage<1>), dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, d_state, d_gres, ws, k & 1);
+				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wseg_grid_block<1>), dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, d_gres, ws, g_pen, k & 1);
 				launches += 2;
 				if ((k & 31) == 31) {
 					MGA_HIP_CHECK(hipGetLastError());
@@ -641,15 +671,57 @@ static int wseg_run(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, const int32_
 			const bool trace = wseg_env("MGA_WFA_SEG_GRID_TRACE", 0, 0, 1) != 0; // one line per launch batch on stderr, the two passes timed apart (one more sync)
 			if (trace && mga_ssync(sc) < 0) return -1;
 			const double t2 = mga_wtime();
-			hipLaunchKernelGGL(k_wseg_grid_p2, dim3(nb), dim3(nt), 0, st,(const wseg_gjob_t*)d_gjob, (const wseg_gres_t*)d_gres, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool,
-							   (long long)jb->pool_cap, jb->d_pool_used, ws, g_pen);
+			double t3 = t2;
+			long long launches2 = 0, mt2 = 0;
+			if (!gp->p2)
+				hipLaunchKernelGGL(k_wseg_grid_p2, dim3(nb), dim3(nt), 0, st,(const wseg_gjob_t*)d_gjob, (const wseg_gres_t*)d_gres, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool,
+								   (long long)jb->pool_cap, jb->d_pool_used, ws, g_pen);
+			else { // ---- the grid-wide form of pass 2: init2 (snapshot walk) | stage, block | ... | tail, its outcome in d_gres2, its halos in the staging areas of pass 1 (half of them)
+				wseg_gres_t *d_gres2 = d_gres + nb;
+				hipLaunchKernelGGL(k_wseg_grid_init2, dim3(nb), dim3(64), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, (const wseg_gres_t*)d_gres, d_gres2, ws);
+				launches2 = 2;
+				// The band of block k is at most min(W, 2 k block + 1) diagonals wide as in pass 1, and, when every checkpoint is taken (step >= 17: wseg_plan), at most
+				// 2 (step + 17) + 1, the width wseg_plan sizes the rows by.  A problem whose band outgrows the grid stops with an error (stage kernel).
+				int64_t wcap = wtop;
+				{
+					int32_t st_lo = 0x7fffffff, st_hi = 0;
+					for (int i = 0; i < nb; ++i) { const int32_t x = gjob[i].J.step; if (x < st_lo) st_lo = x; if (x > st_hi) st_hi = x; }
+					if (st_lo >= WS_NSLOT && 2LL * (st_hi + WS_NSLOT) + 1 < wcap) wcap = 2LL * (st_hi + WS_NSLOT) + 1;
+				}
+				for (int32_t k = 0; k <= s_top; ++k) {
+					const int64_t wb = 2LL * k * gp->block + 1 < wcap ? 2LL * k * gp->block + 1 : wcap;
+					const int gx = (int)(wb / gp->tile > 1 ? wb / gp->tile : 1);
+					hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wseg_grid_stage<2>), dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, d_state, d_gres2, ws, k & 1);
+					hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wseg_grid_block<2>), dim3(gx, nb), dim3(ntg), 0, st, (const wseg_gjob_t*)d_gjob, jb->d_prob, jb->d_tseq, jb->d_qseq, d_state, d_gres2, ws, g_pen, k & 1);
+					launches2 += 2;
+					if ((k & 31) == 31) {
+						MGA_HIP_CHECK(hipGetLastError());
+						if (mga_ssync(sc) < 0 || mga_d2h(gres.data(), d_gres2, (size_t)nb * sizeof(wseg_gres_t)) < 0) return -1;
+						int live = 0;
+						for (int i = 0; i < nb; ++i) live += !gres[i].done;
+						if (!live) break;
+					}
+				}
+				if (trace && mga_ssync(sc) < 0) return -1;
+				t3 = mga_wtime();
+				hipLaunchKernelGGL(k_wseg_grid_tail, dim3(nb), dim3(nt), 0, st,(const wseg_gjob_t*)d_gjob, (const wseg_gres_t*)d_gres2, jb->d_prob, jb->d_tseq, jb->d_qseq, jb->d_res, d_out, jb->d_pool,
+								   (long long)jb->pool_cap, jb->d_pool_used, ws, g_pen);
+				MGA_HIP_CHECK(hipGetLastError());
+				if (mga_ssync(sc) < 0 || mga_d2h(gres.data(), d_gres2, (size_t)nb * sizeof(wseg_gres_t)) < 0) return -1;
+				for (int i = 0; i < nb; ++i) if (gres[i].max_tiles > mt2) mt2 = gres[i].max_tiles;
+				if (mt2 > __atomic_load_n(&g_segg2_max_tiles, __ATOMIC_RELAXED)) __atomic_store_n(&g_segg2_max_tiles, mt2, __ATOMIC_RELAXED);
+				__atomic_fetch_add(&g_segg2_problems, (long long)nb, __ATOMIC_RELAXED);
+				__atomic_fetch_add(&g_segg2_launches, launches2, __ATOMIC_RELAXED);
+			}
 			mga_prof_end(st, kid);
 			MGA_HIP_CHECK(hipGetLastError());
 			if (mga_ssync(sc) < 0 || mga_d2h(gres.data(), d_gres, (size_t)nb * sizeof(wseg_gres_t)) < 0) return -1;
 			long long mt = 0;
 			for (int i = 0; i < nb; ++i) if (gres[i].max_tiles > mt) mt = gres[i].max_tiles;
-			if (trace) fprintf(stderr, "wfa_seg_grid: %d problem(s), tile %d, block %d: pass 1 %.3f s (from the first launch) in %lld launches, pass 2 %.3f s, at most %lld tiles, %lld bytes of workspace\n",
+			if (trace && !gp->p2) fprintf(stderr, "wfa_seg_grid: %d problem(s), tile %d, block %d: pass 1 %.3f s (from the first launch) in %lld launches, pass 2 %.3f s, at most %lld tiles, %lld bytes of workspace\n",
 							   nb, gp->tile, gp->block, t2 - tg0, launches, mga_wtime() - t2, mt, (long long)tot);
+			if (trace && gp->p2) fprintf(stderr, "wfa_seg_grid: %d problem(s), tile %d, block %d: pass 1 %.3f s (from the first launch) in %lld launches, at most %lld tiles; grid-wide pass 2 %.3f s in %lld launches, "
+								 "at most %lld tiles, tail %.3f s; %lld bytes of workspace\n", nb, gp->tile, gp->block, t2 - tg0, launches, mt, t3 - t2, launches2, mt2, mga_wtime() - t3, (long long)tot);
 			if (mt > __atomic_load_n(&g_segg_max_tiles, __ATOMIC_RELAXED)) __atomic_store_n(&g_segg_max_tiles, mt, __ATOMIC_RELAXED);
 			__atomic_fetch_add(&g_segg_problems, (long long)nb, __ATOMIC_RELAXED);
 			__atomic_fetch_add(&g_segg_launches, launches, __ATOMIC_RELAXED);
@@ -685,6 +757,7 @@ extern "C" int mga_dev_wfa_seg(mga_sctx_t *sc, const mga_wfa_job_t *jb, int n, c
 	wseg_grid_par_t gp;
 	gp.tile = (int32_t)wseg_env("MGA_WFA_SEG_GRID_TILE", 1024, 16, 1 << 20);
 	gp.block = (int32_t)wseg_env("MGA_WFA_SEG_GRID_BLOCK", 64, 1, gp.tile < 256 ? gp.tile : 256);
+	gp.p2 = (int32_t)wseg_env("MGA_WFA_SEG_GRID_P2", 1, 0, 1); // (default 1 since the measurement of DESIGN 4: pass 2 in 2.05 s against 4.57-4.60 s; 0: pass 2 on one workgroup)
 	const long long wmin = wseg_env("MGA_WFA_SEG_GRID_MIN", 16384, 0, 1LL << 40);
 	std::vector<int32_t> id[2], tl[2], ql[2];
 	for (int i = 0; i < n; ++i) {

@@ -13,7 +13,7 @@ reference's mwf_wfa_auto().  --rung-only: the same pair through the rung alone (
 the same cells first.  Prints the wall time of the rung, the chosen step, the snapshot count and wfa_seg_bytes.  Needs oracle/_ref/libmgref.so, or
 --ref-cache with an earlier result of it for the same pair.
 
-    python minigraph_amd/tools/wfa_seg_check.py [--len 150000] [--plan-only] [--rung-only] [--ref-cache FILE.npz] [--grid TILE,BLOCK | --grid 0]
+    python minigraph_amd/tools/wfa_seg_check.py [--len 150000] [--plan-only] [--rung-only] [--ref-cache FILE.npz] [--grid TILE,BLOCK | --grid 0] [--p2]
 """
 import argparse
 import ctypes as C
@@ -94,7 +94,10 @@ def main():
     ap.add_argument("--ref-cache", default=None, help="npz file with the reference's result for this pair: read when it matches the pair, written otherwise")
     ap.add_argument("--grid", default=None, metavar="TILE,BLOCK", help="the grid-wide form of the rung's first pass (MGA_WFA_SEG_GRID=1) with this tile and block; "
                     "the library then reports the two passes apart on stderr.  0: the workgroup form (MGA_WFA_SEG_GRID=0).  Not given: the library's defaults")
+    ap.add_argument("--p2", action="store_true", help="the second pass grid-wide as well (MGA_WFA_SEG_GRID_P2=1); needs the grid-wide first pass")
     a = ap.parse_args()
+    if a.p2:
+        os.environ["MGA_WFA_SEG_GRID_P2"] = "1"
     if a.grid == "0":
         os.environ["MGA_WFA_SEG_GRID"] = "0"
     elif a.grid:
@@ -140,6 +143,8 @@ def main():
           % ("wfa_seg_batch" if a.rung_only else "wfa_batch", sc[0], len(cg[0]), wall, st["problems"], L.mga_wfa_seg_seconds(), L.mga_wfa_seg_last_step(), st["snapshots"]))
     if a.grid != "0":
         print("grid-wide first pass (tile,block %s): %s" % (a.grid or "by default",mga.wfa_seg_grid_stats()))
+    if a.p2:
+        print("grid-wide second pass: %s" % mga.wfa_seg_grid_p2_stats())
     cells = L.mga_wfa_seg_cells()
     print("traceback the rung's second pass wrote (one byte per cell of its narrowed band): %d = %.2f GiB" % (cells, cells / 2.0**30))
     if st["problems"] != 1:
